@@ -6,13 +6,19 @@ update + G2P) on the 64M-particle sand column (DruckerPrager, 8 particles/cell, 
 on 1/2/4/8 GPUs of one node (strong scaling: the 64M particles are split spatially, ghost grid blocks exchanged
 over RCCL/xGMI).  Inputs are generated on the device and are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus
   "roofline":     dominant kernel (binned P2G) algorithmic bytes / launch duration (HIP events on the launch stream)
+A plain run sets up, warms up, times the K steps and prints that line.  --full adds the secondary measurements (N=1 only):
   "cpu_baseline": the CPU oracle's OpenMP port of the reference P2G+G2P timed on this box's host cores on a
-                  bounded sample of the same workload (rank 0, N=1 only).
+                  bounded sample of the same workload,
+  "secondary" / "p2g_standalone": sub-runs of this script (column at rest, compact storage, stand-alone P2G, a long
+                  window, BASELINE config 3) and the primitive / bht / TileVector / LBvh rows of SURVEY 8(d),
+  roofline.measured_copy / measured_read (device-copy and read-only stream ceilings), the PMC traffic of profiles/pmc_*.json
+  where it was collected on the same machine code, and "slot_stats" (also with --slot-stats).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -135,8 +141,13 @@ def parse():
                          "interior range, the ghost-block exchange over RCCL (world 1, the rank itself as its only peer, into a scratch grid) "
                          "on the side stream, CFL allreduce -- to measure the fixed per-step host / launch / exchange cost of a rank")
     ap.add_argument("--no-at-rest", action="store_true",
-                    help="skip the secondary measurements (short sub-runs of this script at rest: slotted, compact, unfused stand-alone P2G / G2P; "
-                         "and the primitives / bht / TileVector rows of SURVEY 8(d))")
+                    help="(with --full) skip the secondary measurements (short sub-runs of this script at rest: slotted, compact, unfused "
+                         "stand-alone P2G / G2P; and the primitives / bht / TileVector rows of SURVEY 8(d))")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary measurements: CPU baseline, sub-runs at rest / on compact storage / "
+                         "unfused / long window / config 3, primitive rows, copy and read ceilings, PMC traffic, slot statistics")
+    ap.add_argument("--dump-outputs", type=str, default="",
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32, fixed samples, < 64 MB)")
     return ap.parse_args()
 
 
@@ -262,6 +273,105 @@ def cpu_baseline(sample, dx, dt, model, side, vol):
                       "oracle/mpm.c OpenMP port; best_threads: the same sample at 8 / 16 / 32 / 64 / 128 threads (5 steps each)" % (n, reps)}
 
 
+DUMP_PARTICLE_BYTES = 36 << 20   # --dump-outputs: size of the particle sample ...
+DUMP_GRID_BYTES = 8 << 20        # ... and of the grid sample
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_CELL_SLOTS = 16             # particle rows per sampled cell (the slotted storage's cells hold ~8, rarely more than 13)
+
+
+def _cell_ids(cx, cy, cz):
+    return ((cx + 4096) * 8192 + (cy + 4096)) * 8192 + (cz + 4096)
+
+
+def dump_outputs(out_dir, mt, dx, fused, lo, hi):
+    """--dump-outputs: what the last timed step computed, as float32 / float64 .npy files whose shapes follow from the arguments alone.
+    lo, hi: the cell box the particles can occupy after the run (the column's box swept by its drift and gravity, padded).
+    Particles: the cells of that box a fixed hash of the cell index selects (particle_cell_keys), DUMP_CELL_SLOTS rows per cell
+    holding the particles found in it ordered by (x, y, z), zeros behind them (particle_count); per row x, F (, logJp) -- and v, C
+    where the step stores them (unfused G2P; the fused step keeps them on chip).  The storage order of the particles changes from run
+    to run (movers take their slots by atomic tickets), the cells do not.  Grid: mass and velocity (channels 0..3, after the grid
+    update) of the blocks of the box the same hash of the block key selects, zeros for a block outside the partition."""
+    from zpc_amd.mpm import HAS_LOGJP
+    dev = mt.grid.device
+    S = DUMP_CELL_SLOTS
+    n = mt.n
+    if mt.slotted:
+        cbuf, cnt = mt._compact_copy()
+        if cnt != n:
+            raise SystemExit("--dump-outputs: the slotted storage holds %d particles, %d went in" % (cnt, n))
+        lanes = 64
+    else:
+        cbuf, lanes = mt.buf, mt.L
+    pv = cbuf.view(-1, mt.nchn, lanes)
+    off = mt.off
+    names = [("particle_x", off["x"], 3), ("particle_F", off["F"], mt.nF)]
+    if mt.model in HAS_LOGJP:
+        names.append(("particle_logJp", off["logJp"], 1))
+    if not fused:
+        names += [("particle_v", off["v"], 3), ("particle_C", off["C"], 9)]
+    per_particle = 4 * sum(k for _, _, k in names)
+    # the sampled cells: ascending ids (the enumeration is x-major like the id)
+    ext = [hi[k] - lo[k] for k in range(3)]
+    ncell = ext[0] * ext[1] * ext[2]
+    rate = min(1.0, DUMP_PARTICLE_BYTES / (S * per_particle * ncell))
+    parts = []
+    for s in range(0, ncell, 1 << 24):
+        c = torch.arange(s, min(ncell, s + (1 << 24)), device=dev, dtype=torch.int64)
+        cid = _cell_ids(c // (ext[1] * ext[2]) + lo[0], (c // ext[2]) % ext[1] + lo[1], c % ext[2] + lo[2])
+        parts.append(cid[_hash_uniform(cid, 101) < rate])
+    cells = torch.cat(parts)
+    M = cells.numel()
+    if M == 0:
+        raise SystemExit("--dump-outputs: no cell of the box was sampled")
+    # the particles in them: cell number, then rank by (x, y, z) inside the cell
+    x = pv[:, off["x"]:off["x"] + 3, :].permute(0, 2, 1).reshape(-1, 3)[:n]
+    cell = torch.floor(x.double() / dx).to(torch.int64)
+    pid = _cell_ids(cell[:, 0], cell[:, 1], cell[:, 2])
+    at = torch.searchsorted(cells, pid).clamp_(max=M - 1)
+    idx = torch.nonzero(cells[at] == pid).squeeze(1)
+    xs, sc = x[idx].cpu().numpy(), at[idx].cpu().numpy()
+    order = np.lexsort((xs[:, 2], xs[:, 1], xs[:, 0], sc))
+    idx, sc = idx[torch.from_numpy(order).to(dev)], sc[order]
+    rank = np.arange(sc.shape[0]) - np.searchsorted(sc, sc, side="left")
+    keep = rank < S
+    idx, sc, rank = idx[torch.from_numpy(keep).to(dev)], sc[keep], rank[keep]
+    del x, cell, pid, at
+    cells_h = cells.cpu().numpy()
+    arrays = {"particle_cell_keys": np.stack([cells_h // (8192 * 8192) - 4096, cells_h // 8192 % 8192 - 4096, cells_h % 8192 - 4096], 1).astype(np.float64),
+              "particle_count": np.bincount(sc, minlength=M).astype(np.float32)}
+    for name, c0, k in names:
+        rows = np.zeros((M, S, k), np.float32)
+        rows[sc, rank] = pv[idx // lanes, c0:c0 + k, idx % lanes].cpu().numpy()
+        arrays[name] = rows[:, :, 0] if k == 1 else rows
+    # grid: the sampled blocks of the box (one block of room on every side), looked up in the partition
+    side, nc = mt.side, mt.side ** 3
+    blo = [lo[k] // side - 1 for k in range(3)]
+    bhi = [(hi[k] - 1) // side + 2 for k in range(3)]
+    bk = np.stack(np.meshgrid(*[np.arange(blo[k], bhi[k], dtype=np.int64) for k in range(3)], indexing="ij"), -1).reshape(-1, 3)
+    bid = _cell_ids(bk[:, 0], bk[:, 1], bk[:, 2])
+    bk = bk[(_hash_uniform(torch.from_numpy(bid), 102) < min(1.0, DUMP_GRID_BYTES / (16.0 * nc * bk.shape[0]))).numpy()]
+    keys = mt.active_keys().astype(np.int64)
+    aid = _cell_ids(keys[:, 0], keys[:, 1], keys[:, 2])
+    srt = np.argsort(aid)
+    want = _cell_ids(bk[:, 0], bk[:, 1], bk[:, 2])
+    at = np.searchsorted(aid[srt], want).clip(max=max(aid.shape[0] - 1, 0))
+    found = aid.shape[0] > 0 and (aid[srt][at] == want)
+    g = np.zeros((bk.shape[0], 4, nc), np.float32)
+    if np.any(found):
+        blocks = torch.from_numpy(srt[at[found]]).to(dev)
+        g[found] = mt.grid.view(-1, 7, nc)[blocks, 0:4].cpu().numpy()
+    arrays["grid_block_keys"] = bk.astype(np.float64)
+    arrays["grid_mass"] = g[:, 0, :]
+    arrays["grid_velocity"] = g[:, 1:4, :]
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+    return {name: list(v.shape) for name, v in arrays.items()}
+
+
 def main():
     a = parse()
     a.fused = not (a.unfused or a.unbinned or a.no_cache_stress)
@@ -279,6 +389,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if a.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs: single-rank runs only")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the product path has no CPU fallback)")
     if a.same_device:
@@ -792,6 +904,15 @@ def main():
         wgs = max(int(pv[7]), 1)
         print("probe (cycles per workgroup, 100 MHz-agnostic s_memtime ticks): " +
               " ".join("[%d]=%.0f" % (k, pv[k] / wgs / (4 if k in (0, 1, 4, 5, 6) else 8)) for k in range(7)) + " wgs=%d" % wgs, file=sys.stderr)
+    dumped = None
+    if a.dump_outputs:   # (before the untimed write_all step below, which would advance the state once more)
+        # where the column can be after the run: its box swept by the drift and by gravity (upper bound, 4 cells of room for the
+        # particles' own velocities) -- set by the arguments, so is every shape the dump writes
+        t_run = (a.warmup + a.steps) * dt
+        sweep = [drift_v[k] * t_run / dx - (0.5 * 9.8 * t_run * t_run / dx if k == 1 else 0.0) for k in range(3)]
+        box_lo = [glo[k] + int(np.floor(min(0.0, sweep[k]))) - 4 for k in range(3)]
+        box_hi = [ghi[k] + int(np.ceil(max(0.0, sweep[k]))) + 4 for k in range(3)]
+        dumped = dump_outputs(a.dump_outputs, mt, dx, a.fused, box_lo, box_hi)
     if a.fused and (a.checksum or a.dump_state):
         step_fused(False, write_all=True)  # untimed: materialise v, C, stress of every particle for the checksum
         torch.cuda.synchronize()
@@ -848,7 +969,7 @@ def main():
                                   "allreduce(max); exchange_side_stream_ms = pack + grouped ncclSend/ncclRecv + unpack-add on the side stream "
                                   "(overlaps the interior range)"}
     slot_stats = None
-    if a.slotted:
+    if a.slotted and (a.slot_stats or a.full):
         # occupancy of the slotted storage at the end of the run: rounds a bin's producers walk (highest occupied round + 1, in chunks of
         # four) against the particles it holds
         m = mt.cell_mask.view(mt.nbins, 64).to(torch.int64) & 0xFFFFFFFF
@@ -926,7 +1047,7 @@ def main():
         ach = p2g_bytes * n_local / (max(p2g_ms, 1e-9) * 1e-3) / 1e9
         traffic = None
         pmc = os.path.join(ROOT, "profiles", "pmc_p2g.json")
-        if os.path.exists(pmc):
+        if a.full and os.path.exists(pmc):
             try:
                 j = json.load(open(pmc))
                 if (j.get("particles") == n_local and j.get("side") == a.side and j.get("model") == a.model
@@ -991,7 +1112,7 @@ def main():
             fkernel = (("g2p2g_slot_kernel" if per_bin else "g2p2g_slotblk_kernel") + " + slot_rehome_kernel + slot_commit_kernel") if a.slotted else "g2p2g_rs_kernel"
             fvalu = None
             pmcf = os.path.join(ROOT, "profiles", "pmc_g2p2g.json" if (a.slotted and moving) else "pmc_g2p2g_compact.json")
-            if os.path.exists(pmcf) and (a.slotted == moving):
+            if a.full and os.path.exists(pmcf) and (a.slotted == moving):
                 try:
                     j = json.load(open(pmcf))
                     if (j.get("particles") == n_local and j.get("side") == a.side and j.get("model") == a.model and j.get("kernel") == fkernel
@@ -1041,38 +1162,41 @@ def main():
                     out["roofline"]["bound"] = "valu"
         # the measured device-copy ceiling of THIS box beside the nominal peak (1 GiB device-to-device copies, read + write
         # bytes over HIP-event time, after the timed region)
-        try:
-            ca = torch.empty(1 << 28, dtype=torch.float32, device=device)
-            cb = torch.empty_like(ca)
-            cb.copy_(ca)
-            ce = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ce[0].record()
-            for _ in range(5):
+        if a.full:
+            try:
+                ca = torch.empty(1 << 28, dtype=torch.float32, device=device)
+                cb = torch.empty_like(ca)
                 cb.copy_(ca)
-            ce[1].record()
-            torch.cuda.synchronize()
-            copy_gbs = 2.0 * ca.numel() * 4 * 5 / (ce[0].elapsed_time(ce[1]) * 1e-3) / 1e9
-            del ca, cb
-            out["roofline"]["measured_copy"] = copy_gbs
-            out["roofline"]["frac_of_measured_copy"] = out["roofline"]["achieved"] / copy_gbs
-            # ... and the read-only stream ceiling (P2G is 80 % reads: the copy ceiling understates what a read-dominated kernel can
-            # reach): zs::reduce<i32, plus> over 1 GiB, HIP-event time on the policy's stream
-            import zpc_amd as _zs
-            ra = torch.zeros(1 << 28, dtype=torch.int32, device=device)
-            r1 = torch.zeros(1, dtype=torch.int32, device=device)
-            _zs.reduce(pol, ra, None, r1)
-            ce = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ce[0].record()
-            for _ in range(5):
+                ce = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ce[0].record()
+                for _ in range(5):
+                    cb.copy_(ca)
+                ce[1].record()
+                torch.cuda.synchronize()
+                copy_gbs = 2.0 * ca.numel() * 4 * 5 / (ce[0].elapsed_time(ce[1]) * 1e-3) / 1e9
+                del ca, cb
+                out["roofline"]["measured_copy"] = copy_gbs
+                out["roofline"]["frac_of_measured_copy"] = out["roofline"]["achieved"] / copy_gbs
+                # ... and the read-only stream ceiling (P2G is 80 % reads: the copy ceiling understates what a read-dominated kernel can
+                # reach): zs::reduce<i32, plus> over 1 GiB, HIP-event time on the policy's stream
+                import zpc_amd as _zs
+                ra = torch.zeros(1 << 28, dtype=torch.int32, device=device)
+                r1 = torch.zeros(1, dtype=torch.int32, device=device)
                 _zs.reduce(pol, ra, None, r1)
-            ce[1].record()
-            torch.cuda.synchronize()
-            read_gbs = ra.numel() * 4 * 5 / (ce[0].elapsed_time(ce[1]) * 1e-3) / 1e9
-            del ra
-            out["roofline"]["measured_read"] = read_gbs
-            out["roofline"]["frac_of_measured_read"] = out["roofline"]["achieved"] / read_gbs
-        except Exception:
-            pass
+                ce = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ce[0].record()
+                for _ in range(5):
+                    _zs.reduce(pol, ra, None, r1)
+                ce[1].record()
+                torch.cuda.synchronize()
+                read_gbs = ra.numel() * 4 * 5 / (ce[0].elapsed_time(ce[1]) * 1e-3) / 1e9
+                del ra
+                out["roofline"]["measured_read"] = read_gbs
+                out["roofline"]["frac_of_measured_read"] = out["roofline"]["achieved"] / read_gbs
+            except Exception:
+                pass
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
         if checksum is not None:
             out["checksum"] = checksum
             out["checksum_trimmed"] = {"sums": checksum_trim[:-1], "trimmed_particles": int(checksum_trim[-1]),
@@ -1084,7 +1208,7 @@ def main():
         if comm is not None:
             out["config"]["nccl_comm_count"] = int(lib().zs_rocm_dist_comm_count(comm._h))
             out["config"]["gpus_visible"] = torch.cuda.device_count()
-        if world == 1 and a.slotted and not a.no_at_rest and any(abs(x) > 0 for x in drift_v):
+        if a.full and world == 1 and a.slotted and not a.no_at_rest and any(abs(x) > 0 for x in drift_v):
             # secondary numbers: the same column at rest (no movers) -- short sub-runs of this script after the timed region
             import subprocess
             try:
@@ -1130,7 +1254,7 @@ def main():
                             "P2G.hpp orders it; unfused_step_frac: P2G + G2P launches together (where the moved update is paid); "
                             "frac_of_measured_read: against this box's read-only stream rate instead of the nominal 8 TB/s"})
                 # the headline over a long window: steps 100-200 of a 200-step run (fresh storage flatters the first steps)
-                js = sub(["--drift", ",".join(str(x) for x in drift_v), "--steps", "100", "--warmup", "100"])
+                js = sub(["--drift", ",".join(str(x) for x in drift_v), "--steps", "100", "--warmup", "100", "--slot-stats"])
                 out["secondary"]["sustained"] = {"ms_per_step": js["ms_per_step"], "roofline_frac": js["roofline"]["frac"], "steps": "100-200 of a 200-step run",
                                                  "repartitions": js["config"].get("repartitions"),
                                                  "mean_rounds": (js.get("slot_stats") or {}).get("mean_rounds")}
@@ -1143,7 +1267,7 @@ def main():
             except Exception as e:
                 out["config"]["at_rest_ms_per_step"] = None
                 print("at-rest runs failed: %r" % (e,), file=sys.stderr)
-        if world == 1 and not a.no_at_rest:
+        if a.full and world == 1 and not a.no_at_rest:
             # SURVEY 8(d) secondary metrics (BASELINE configs 1, 2 and 5): reduce / exclusive_scan / radix_sort(_pair) at 1 M and 64 M ints,
             # bht build over 16 M random particles, TileVector<f32,32> 25-channel load + store at 16 M, LBvh build / refit / queries /
             # self-collision broadphase at 10 M boxes -- each {ms, units_per_s, frac}
@@ -1156,7 +1280,7 @@ def main():
                      "bytes_per_unit": r["algorithmic_bytes_per_unit"], "frac": r["frac_of_8TBps"]} for r in rows]
             except Exception as e:
                 print("secondary primitives failed: %r" % (e,), file=sys.stderr)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.cpu_sample, dx, dt, model, a.side, vol)
         print(json.dumps(out), flush=True)
     if dist is not None:

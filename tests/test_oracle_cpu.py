@@ -87,16 +87,23 @@ def test_hash_matches_reference_golden(oracle):
     assert oracle.orc_bht_table_size(C.c_size_t(200000)) == 524304
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libzpcref.so")), reason="reference build only exists in the build container")
 def test_oracle_vs_live_reference_build(oracle):
-    ref = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libzpcref.so"))
+    """singular values of the oracle's svd against the reference's: the live oracle/_ref build where it exists, else the values that
+    build gave for the same matrices (tests/golden/svd_live.npz, tools/gen_golden.py)"""
+    lib = os.path.join(ROOT, "oracle", "_ref", "libzpcref.so")
+    ref = C.CDLL(lib) if os.path.exists(lib) else None
     g = rng(50)
     F = (np.eye(3).reshape(1, 9) + 0.15 * g.standard_normal((3000, 9))).astype(np.float32)
+    stored = np.load(os.path.join(GOLD, "svd_live.npz"))
+    assert np.array_equal(stored["F"], F)
     S1, S2 = np.zeros(3, np.float32), np.zeros(3, np.float32)
     U, V = np.zeros(9, np.float32), np.zeros(9, np.float32)
     for i in range(F.shape[0]):
         oracle.orc_svd3(ptr(F[i]), ptr(U), ptr(S1), ptr(V))
-        ref.ref_svd3(ptr(F[i]), ptr(U), ptr(S2), ptr(V))
+        if ref is not None:
+            ref.ref_svd3(ptr(F[i]), ptr(U), ptr(S2), ptr(V))
+        else:
+            S2 = stored["S"][i]
         assert np.abs(S1 - S2).max() < 3e-6
 
 

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 for n in "$@"; do
   for rep in 1 2; do
-    ZS_ROCM_LIB=$R/zpc_amd/lib/ablate/libzsrocm_$n.so python bench.py --no-at-rest --no-cpu-baseline $ABFLAGS 2>/tmp/ab_err.txt | python -c "
+    ZS_ROCM_LIB=$R/zpc_amd/lib/ablate/libzsrocm_$n.so python bench.py --slot-stats $ABFLAGS 2>/tmp/ab_err.txt | python -c "
 import sys, json
 l = [x for x in sys.stdin if x.startswith('{')]
 d = json.loads(l[-1]) if l else {}

@@ -223,6 +223,20 @@ def gen_grid_arena():
     print("grid_arena.npz: %d cases x %d points" % (len(cases), npts))
 
 
+def gen_svd_live():
+    """The singular values the reference's svd gives for the 3000 matrices of test_oracle_vs_live_reference_build (tests/util.py rng(50)):
+    the test compares against the live build where it exists and against these values everywhere else."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from util import rng
+    g = rng(50)
+    F = (np.eye(3).reshape(1, 9) + 0.15 * g.standard_normal((3000, 9))).astype(np.float32)
+    S = np.zeros((F.shape[0], 3), np.float32)
+    U, V = np.zeros(9, np.float32), np.zeros(9, np.float32)
+    for i in range(F.shape[0]):
+        ref.ref_svd3(P(F[i]), P(U), P(S[i]), P(V))
+    np.savez_compressed(os.path.join(OUT, "svd_live.npz"), F=F, S=S)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     g = np.random.Generator(np.random.PCG64(0x9E3779B97F4A7C15 ^ 77))
@@ -366,6 +380,7 @@ def main():
     gen_containers_seq()
     gen_grid_arena()
     gen_c2()
+    gen_svd_live()
     print("wrote", os.listdir(OUT))
 
 
