@@ -38,7 +38,8 @@ struct SlotArgs {
   const int *nbr;       // [nblocks][8]  blocks at offsets {0,1}^3 (arena -> grid)
   const int *nbr27;     // [nblocks][27] blocks at offsets {-1,0,1}^3 (movers: arena flush, destination bin)
   int *moverCount;      // [nbins] movers of the bin in this step (diagnostic)
-  unsigned *claim;      // [2][nbinsAll][64]: [0] this step's arrivals (high 16 bits: from inside the bin, low 16: from other bins), [1] rounds
+  unsigned *claim;      // [2][nbinsAll][64]: [0] this step's arrivals (high 16 bits: from inside the bin -- the block kernel: from inside
+                        // the block --, low 16: from the other bins, counted by slot_rehome_kernel), [1] rounds
                         // vacated in this step; zero between steps (slot_commit_kernel folds both into cellMask)
   float *moverRec;      // [nbins][cap][SL_REC] outbox records: movers that left their bin (or found the arrival queue of their cell full)
   int *status;          // [0] outbox full, [1] cell full (K), [2] mass / a mover for a block outside the partition, [3] a particle lives in a
@@ -95,7 +96,11 @@ template <int SIDE> __device__ __forceinline__ int neighbour_bin(const int *nbr2
 //     dependence between records.  (Measured dead ends: ds_add_f32 into a wider LDS arena, ~3 cycles per lane: +4 ms; returning
 //     global ticket atomics in the producer loop: ~5 us round trip under load, +2.6 ms; one wave per channel walking the records with
 //     plain LDS read-add-write: latency-bound, 6 us per workgroup.)  The record's new home is found by slot_rehome_kernel after the
-//     step: one thread per record, ticket from the destination cell's global counter, rounds above the in-bin arrivals.
+//     step: one thread per record, ticket from the destination cell's global counter, rounds above the in-bin arrivals;
+//   * (r07, block kernel only: INBLK) new cell in another bin of the SAME 8^3 block: re-slotted by the producer like an in-bin mover --
+//     ticket of the destination bin's LDS counter (the workgroup keeps all eight for the step), state stored straight into the free
+//     round -- while its grid terms take the list as above; no record, no slot_rehome_kernel.  The claim words' high halves then count
+//     the arrivals from inside the block, written once per block after its last barrier.
 // Departures and ticket counts are folded into the occupancy words by slot_commit_kernel.
 #ifndef ZS_PROD_XLIST
 #define ZS_PROD_XLIST 1  // the list of the last chunk is scattered by the (then idle) producer waves
@@ -268,13 +273,18 @@ struct SlotBinView {
   unsigned *arrLocal;   // [64] in-bin arrivals of the cell in this step (ticket counter)
   const int *nbrBin;    // [27] the bins around this one (direction code (dx + 1) 9 + (dy + 1) 3 + dz + 1)
   int *outCount, *sent, *homed, *xOver;
+  unsigned (*arrBlk)[64];         // INBLK (block kernel): [8][64] ticket counters of ALL bins of the block, for the step (arrLocal = arrBlk[bin & 7])
+  const unsigned (*maskBlk)[64];  // INBLK: [8][64] occupancy of the block's bins at the start of the step (mask0 = maskBlk[bin & 7])
 };
 
 // One occupied slot of a bin: G2P from the velocity arena, advection, F update, constitutive update, the particle's new state to its
 // (old or new) slot or to an outbox record, {m, d0, Q-form coefficients} staged at `myStage` (staged position `spos` = ring group * 64 +
 // lane) after beforeStage() -- the hook in which the block kernel waits until the consumers have released the ring slot.  code0 = round * 64 + cell of the slot, i0 = its element index.  Returns whether the lane of the slot's cell consumes the staged
 // record (a stayer); movers are queued for the lane of their new cell (arrCnt / arrQ) or for the global-atomic list (xCnt / xq).
-template <int SIDE, int SMODEL, bool WRITE_ALL, class VA, class REC, class WAIT>
+// INBLK (block kernel only, bin = one of the 8 bins of an 8^3 block): a mover whose new cell lies in ANOTHER bin of the same block is
+// re-slotted here like an in-bin mover -- ticket of that bin's counter (arrBlk), the t-th round that was free in it at the start of the
+// step (maskBlk), state stored straight into that slot -- and its grid terms take the consumers' list as before; no outbox record.
+template <int SIDE, int SMODEL, bool WRITE_ALL, class VA, bool INBLK = false, class REC, class WAIT>
 __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const ParticlesDev &ps, const REC &cur, unsigned code0, size_t i0, int lane,
                                                    unsigned spos, float *myStage, const SlotBinView &bv, const SlotArgs &A, unsigned *arrCnt,
                                                    unsigned short (*arrQ)[SL_ARRQ], unsigned *xCnt, unsigned *xq, WAIT beforeStage,
@@ -321,9 +331,9 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
     // (InterpolationKernel.hpp:108 on simulation/Utils.hpp:59-60; make_arena restates it).  The lane = cell consumers take the staged
     // lpn as d0; such a particle is scattered through the consumers' list instead, which folds d0 as the reference does.
     const bool edge = !(lpn[0] >= 0.5f && lpn[0] < 1.5f && lpn[1] >= 0.5f && lpn[1] < 1.5f && lpn[2] >= 0.5f && lpn[2] < 1.5f);
-        bool outbox = false;   // it gets an outbox record (new cell in a neighbour bin: slot_rehome_kernel finds its slot; or fallback scatter)
+    bool outbox = false;   // it gets an outbox record (new cell in another block / bin: slot_rehome_kernel finds its slot; or fallback scatter)
     bool staged = !moved;  // {m, x', v', C', P F^T} staged for the consumers
-    bool home = false;     // mover with a new slot inside this bin
+    bool home = false;     // mover with a new slot (inside this bin; INBLK: inside this block)
     bool byList = false;   // stayer scattered by the consumers' list (see `edge`)
     bool lowered = false;  // stayer re-homed into a lower round of its own cell
     bool keep = false;     // mover that found no new home (cell full, outbox full, moved too far): it stays in its OLD slot with its new
@@ -342,34 +352,39 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
       const int dl = ((nc[0] & 3) * 4 + (nc[1] & 3)) * 4 + (nc[2] & 3);
       unsigned dcell = 0xffffffffu;  // destination cell of a record whose home slot_rehome_kernel has to find
       bool viaX = true;              // its grid contributions: consumers' global-atomic list (else: arrival queue of its new cell)
+      const int dbin = far ? -1 : (code == 13 ? bv.bin : bv.nbrBin[code]);
+      // new cell in this bin, or (INBLK) in another bin of this block: re-slotted here
+      const bool local = !far && (INBLK ? dbin >= 0 && (dbin >> 3) == (bv.bin >> 3) : code == 13);
       if (far) {
         A.status[4] = 1;  // moved more than one cell in one step (CFL violated): not representable (scattered nowhere)
         viaX = false;
         keep = true;
-      } else if (code == 13) {  // new cell inside this bin: a ticket of its LDS counter = a free round, from the bottom
-        const int rr = nth_low_bit(~bv.mask0[dl] & bv.kmask, atomicAdd(&bv.arrLocal[dl], 1u));
+      } else if (local) {  // a ticket of the destination bin's LDS counter = a free round of the cell, from the bottom
+        unsigned *const arr = INBLK ? bv.arrBlk[dbin & 7] : bv.arrLocal;
+        const unsigned m0 = INBLK ? bv.maskBlk[dbin & 7][dl] : bv.mask0[dl];
+        const int rr = nth_low_bit(~m0 & bv.kmask, atomicAdd(&arr[dl], 1u));
         if (rr >= 0) {
           home = true;
-          o = particle_offset<LW>(ps.pos.chns, (bv.rowBase + (size_t)rr) * 64 + (size_t)dl);
+          const size_t row = INBLK ? (size_t)dbin * (size_t)A.K : bv.rowBase;
+          o = particle_offset<LW>(ps.pos.chns, (row + (size_t)rr) * 64 + (size_t)dl);
         } else {
           A.status[1] = 1;  // cell full: the particle is scattered but has no new slot
           keep = true;
         }
-        const unsigned q = edge ? (unsigned)SL_ARRQ : atomicAdd(&arrCnt[dl], 1u);
-        if (q < (unsigned)SL_ARRQ) {  // the lane of the new cell scatters it (arrival queue of the chunk)
-          viaX = false;
-          staged = true;
-          arrQ[dl][q] = (unsigned short)spos;
+        if (code == 13) {  // the lane of the new cell scatters it (arrival queue of the chunk), unless the queue is full
+          const unsigned q = edge ? (unsigned)SL_ARRQ : atomicAdd(&arrCnt[dl], 1u);
+          if (q < (unsigned)SL_ARRQ) {
+            viaX = false;
+            staged = true;
+            arrQ[dl][q] = (unsigned short)spos;
+          }
         }
+      } else if (dbin >= 0) {
+        outbox = true;
+        dcell = (unsigned)dbin * 64u + (unsigned)dl;
       } else {
-        const int dbin = bv.nbrBin[code];
-        if (dbin >= 0) {
-          outbox = true;
-          dcell = (unsigned)dbin * 64u + (unsigned)dl;
-        } else {
-          A.status[2] = 1;  // the destination block is not in the partition: the particle keeps its old slot with its new state
-          keep = true;      // (never dropped: G2P.hpp:67-82 writes every particle back); the caller re-partitions and re-slots
-        }
+        A.status[2] = 1;  // the destination block is not in the partition: the particle keeps its old slot with its new state
+        keep = true;      // (never dropped: G2P.hpp:67-82 writes every particle back); the caller re-partitions and re-slots
       }
       if (viaX) {
         const unsigned k = atomicAdd(xCnt, 1u);
@@ -377,7 +392,7 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
           staged = true;
           xq[k] = spos | ((unsigned)(nc[0] + 1) << 10) | ((unsigned)(nc[1] + 1) << 13) |
                        ((unsigned)(nc[2] + 1) << 16);
-        } else {  // list full: a full record, scattered after the loop
+        } else {  // list full: a full record, scattered after the loop (SLR_DCELL = ~0 for a mover that already has its new slot)
           outbox = true;
           recFlag = 1u;
           atomicAdd(bv.xOver, 1);
@@ -411,8 +426,8 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
           pstore<LW, 3>(ps.vel, o, vel);
           pstore<LW, 9>(ps.C, o, C);
         }
-        if (home) atomicAdd(bv.homed, 1);
       }
+      if (home) atomicAdd(bv.homed, 1);
       if (!keep) {
         atomicOr(&bv.clr[cell], 1u << r);  // its slot becomes a hole
         atomicAdd(bv.sent, 1);
@@ -451,6 +466,7 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
         }
       }
     }
+    const bool stored = !moved || home || keep;  // the particle's state is in its own, lowered, new or old slot (else: in its record)
     SLP_SEG(2);  // tickets / queues / records of the movers, the particle's stores
     {  // the plastic models may project the local copy of F (the stored / recorded F is the unprojected one, P2G.hpp:101)
       float lj = plj;
@@ -466,7 +482,7 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
           }
         }
       }
-      if (!moved || home || keep) {
+      if (stored) {
         if constexpr (DP) pstore1<LW>(ps.logJp, o, lj);
         if (WRITE_ALL) {
           float S[STRESS_N];
@@ -515,7 +531,7 @@ __device__ __forceinline__ void g2p2g_slot_producer(const MpmDev &mp, const Part
   unsigned(*const xq)[SL_XQ] = sh.xq;
   int *const outCount = sh.outCount, *const sent = sh.sent, *const homed = sh.homed, *const xOver = sh.xOver;
   const SlotBinView bv{bin, {geo.org[0], geo.org[1], geo.org[2]}, rowBase, kmask, sh.varena, sh.mask0, sh.clr, sh.arrLocal, sh.nbrBin,
-                       sh.outCount, sh.sent, sh.homed, sh.xOver};
+                       sh.outCount, sh.sent, sh.homed, sh.xOver, nullptr, nullptr};
   RecG<LW, DP, FLUID> cur, nxt;
   bool has0 = false, has1 = false;
   size_t i0 = 0, i1 = 0;

@@ -16,8 +16,11 @@
 //     hands the staged chunk over;
 //   * per-bin state (entry table, tickets, departures, outbox count, neighbour bins) is double-buffered by bin parity and kept by the
 //     CONSUMER waves, which have the time: the entry table of a bin is built three chunks ahead, its neighbour bins two chunks ahead,
-//     a finished bin's claim words are written out with its last chunk (blk_consumer spells out when each buffer is free); everything
+//     a finished bin's departures are written out with its last chunk (blk_consumer spells out when each buffer is free); everything
 //     the loops need to know about a chunk sits in one packed word (ChunkDesc), read once per iteration into SGPRs;
+//   * (r07) the ticket counters of all eight bins live for the whole workgroup (s_arrLocal[8][64]): a mover into another bin of the
+//     block takes its new slot here (slot_produce_entry, INBLK) instead of an outbox record and a slot_rehome_kernel ticket -- about
+//     half of all cross-bin movers.  The arrivals per cell (claim words, high half) are written once, after the block's last barrier;
 //   * 128 VGPRs and NO scratch: the uniform constants of the per-particle code come from the host (MpmDev::dxi, D_inv, fscale;
 //     Material::smu, dpCoef, expCohesion -- kernel arguments live in SGPRs), one producer body serves the four producer waves.  On gfx9
 //     loads and stores share vmcnt, so a spill reload inside the chunk loop waits for the record prefetch of the next chunk and for the
@@ -51,7 +54,8 @@ struct BlkShared {
   unsigned long long *smask;
   unsigned short (*tab)[SL_KMAX * 64];       // [2]
   unsigned (*masks)[64];                     // [8]
-  unsigned (*clr)[64], (*arrLocal)[64];      // [2]
+  unsigned (*clr)[64];                       // [2]
+  unsigned (*arrLocal)[64];                  // [8]: ticket counters of the block's bins, for the whole step (in-block movers)
   unsigned (*arrCnt)[64];                    // [3]
   unsigned short (*arrQ)[64][SL_ARRQ];       // [3]
   unsigned *xCnt;                            // [3]
@@ -115,17 +119,15 @@ __device__ __forceinline__ int blk_neighbour_bin(const int *nbrBlk, int blk, int
   return nb < 0 ? -1 : nb * 8 + ((sx[0] * 2 + sx[1]) * 2 + sx[2]);
 }
 
-// a finished bin (all of its chunks produced by all producer waves): departures and in-bin arrivals of its cells for slot_rehome_kernel /
-// slot_commit_kernel, its outbox count; the parity's counters are zero again.  One wave, lane = cell; every LDS read is issued before the
+// a finished bin (all of its chunks produced by all producer waves): departures of its cells for slot_rehome_kernel / slot_commit_kernel,
+// its outbox count; the parity's counters are zero again (its arrivals can still grow: the kernel writes them after its last barrier).  One wave, lane = cell; every LDS read is issued before the
 // first use (ONE round trip: as a chain of lane-0 reads this was 4.9 k cycles per bin on the producers' critical path, r05 stamps).
 __device__ __forceinline__ void blk_finish_bin(const BlkShared &sh, const SlotArgs &A, int bin0, int b, int qp, int lane) {
   const int bin = bin0 + b;
-  const unsigned c = sh.clr[qp][lane], nl = sh.arrLocal[qp][lane];
+  const unsigned c = sh.clr[qp][lane];
   const int cv = sh.cnt[qp][lane & 3];  // outCount, sent, homed, xOver
   if (c) A.claim[((size_t)A.nbinsAll + (size_t)bin) * 64 + lane] = c;
-  if (nl) A.claim[(size_t)bin * 64 + lane] = nl << 16;  // (the low half -- arrivals from other bins -- is counted by slot_rehome_kernel)
   sh.clr[qp][lane] = 0u;
-  sh.arrLocal[qp][lane] = 0u;
   const int c0 = __builtin_amdgcn_readlane(cv, 0), c1 = __builtin_amdgcn_readlane(cv, 1), c2 = __builtin_amdgcn_readlane(cv, 2),
             c3 = __builtin_amdgcn_readlane(cv, 3);
   if (lane == 0) {
@@ -276,8 +278,8 @@ __device__ __forceinline__ void blk_producer(const MpmDev &mp, const ParticlesDe
     // consumer waves, which have the time: see blk_consumer)
     const SubGeom sg = sub_geom(borg, b);
     const SlotBinView bv{bin0 + b, {sg.org[0], sg.org[1], sg.org[2]}, (size_t)(bin0 + b) * (size_t)A.K, kmask,
-                         sh.varena + ArenaBlk::at(sg.o[0], sg.o[1], sg.o[2]), sh.masks[b], sh.clr[qp], sh.arrLocal[qp], sh.nbrBin[qp],
-                         &sh.cnt[qp][0], &sh.cnt[qp][1], &sh.cnt[qp][2], &sh.cnt[qp][3]};
+                         sh.varena + ArenaBlk::at(sg.o[0], sg.o[1], sg.o[2]), sh.masks[b], sh.clr[qp], sh.arrLocal[b], sh.nbrBin[qp],
+                         &sh.cnt[qp][0], &sh.cnt[qp][1], &sh.cnt[qp][2], &sh.cnt[qp][3], sh.arrLocal, sh.masks};
     // the ring slot this wave stages into was last read by the consumers of chunk g - 1 (its groups 0..2, or the straddle group of
     // chunk g - 2, consumed with chunk g - 1): all four consumer waves have counted that chunk done
     auto ringFree = [&] {
@@ -287,7 +289,7 @@ __device__ __forceinline__ void blk_producer(const MpmDev &mp, const ParticlesDe
     bool valid = false;
     SLP_ACC(tPre, tIt);
     if (has0)
-      valid = slot_produce_entry<8, SMODEL, WRITE_ALL, ArenaBlk>(mp, ps, cur, code0, elem(b, code0), lane, (unsigned)(slot * 64 + lane), myStage + lane, bv, A,
+      valid = slot_produce_entry<8, SMODEL, WRITE_ALL, ArenaBlk, true>(mp, ps, cur, code0, elem(b, code0), lane, (unsigned)(slot * 64 + lane), myStage + lane, bv, A,
                                                                  sh.arrCnt[par], sh.arrQ[par], &sh.xCnt[par], sh.xq[par], ringFree, seg);
     SLP_T0(tR);
     ringFree();
@@ -481,7 +483,7 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   __shared__ unsigned long long s_smask[SB_NG];
   __shared__ unsigned short s_tab[2][SL_KMAX * 64];
   __shared__ unsigned s_masks[8][64];
-  __shared__ unsigned s_clr[2][64], s_arrLocal[2][64], s_arrCnt[3][64];
+  __shared__ unsigned s_clr[2][64], s_arrLocal[8][64], s_arrCnt[3][64];
   __shared__ unsigned short s_arrQ[3][64][SL_ARRQ];
   __shared__ unsigned s_xCnt[3], s_xq[3][SL_XQ];
   __shared__ int s_nbrBlk[27], s_nbrBin[2][27], s_nbr8[8];
@@ -500,16 +502,14 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   // occupancy of the block's 8 bins: wave w <-> bin w
   const unsigned mask = A.cellMask[(size_t)(bin0 + w) * 64 + lane];
   s_masks[w][lane] = mask;
+  s_arrLocal[w][lane] = 0u;
   {
     int n = __popc(mask);
 #pragma unroll
     for (int sft = 32; sft >= 1; sft >>= 1) n += __shfl_xor(n, sft, 64);
     if (lane == 0) s_total[w] = n;
   }
-  if (tid < 128) {
-    s_clr[tid >> 6][tid & 63] = 0u;
-    s_arrLocal[tid >> 6][tid & 63] = 0u;
-  }
+  if (tid < 128) s_clr[tid >> 6][tid & 63] = 0u;
   if (tid < 192) s_arrCnt[tid >> 6][tid & 63] = 0u;
   if (tid < 3) {
     s_xCnt[tid] = 0u;
@@ -586,6 +586,11 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
     else blk_consumer<3>(mp, borg, blk, lane, G, sh, A);
   }
   __syncthreads();  // the last bin is finished (blk_finish_bin by the consumer wave of set 3)
+  {  // this step's arrivals from inside the block per cell (in-bin and in-block movers, lowered stayers: all tickets drawn), thread = (bin, cell).
+     // High half of the claim word: slot_rehome_kernel puts the arrivals from other blocks above them (low half)
+    const unsigned nl = s_arrLocal[w][lane];
+    if (nl) A.claim[(size_t)(bin0 + w) * 64 + lane] = nl << 16;
+  }
   if (w == 0) {
     SLP_ADD(0, tStart);
     SLP_PUT(11, 1);
