@@ -289,37 +289,13 @@ __device__ __forceinline__ void load_box2_agent(const AABB3 *pl, const AABB3 *pr
   L.lo[0] = a.x; L.lo[1] = a.y; L.lo[2] = a.z; L.hi[0] = a.w; L.hi[1] = c.x; L.hi[2] = c.y;
   R.lo[0] = d.x; R.lo[1] = d.y; R.lo[2] = d.z; R.hi[0] = d.w; R.hi[1] = e.x; R.hi[2] = e.y;
 }
-// _refit_bottom_up (Bvh.hpp:469-492): the second lane to arrive at a trunk node merges its children and climbs
-__global__ __launch_bounds__(256) void lbvh_refit_kernel(int numLeaves, const AABB3 *primBvs, AABB3 *orderedBvs, const int *auxIndices,
-                                                         const int *leafInds, const int *parents, const int *levels, int *flags) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= numLeaves) return;
-  int node = leafInds[idx];
-  store_box_agent(orderedBvs + node, primBvs[auxIndices[node]]);
-  node = parents[node];
-  while (node != -1) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this lane's box is at the coherence point before it signs in
-    if (atomicCAS(&flags[node], 0, 1) == 0) break;     // first to arrive: the sibling will do the merge
-    const int lc = node + 1;
-    const int rc = levels[lc] ? auxIndices[lc] : lc + 1;
-    AABB3 L, R;
-    load_box2_agent(orderedBvs + lc, orderedBvs + rc, L, R);
-    AABB3 bv;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      bv.lo[d] = fminf(L.lo[d], R.lo[d]);
-      bv.hi[d] = fmaxf(L.hi[d], R.hi[d]);
-    }
-    store_box_agent(orderedBvs + node, bv);
-    node = parents[node];
-  }
-}
-// The same refit, windowed (r04).  In the pre-order layout the subtree of node p occupies the positions [p, esc(p)), so a workgroup that
+// _refit_bottom_up (Bvh.hpp:469-492): the second lane to arrive at a trunk node merges its children and climbs.  Windowed (r04): in
+// the pre-order layout the subtree of node p occupies the positions [p, esc(p)), so a workgroup that
 // owns a window [P0, P1) of positions can finish every subtree that lies inside it on its own: boxes, arrival flags and the topology of
 // the window live in LDS, and only the nodes whose subtree sticks out of the window (p < P0 or esc(p) > P1: ~1 % of the nodes at 2048
-// positions per window) take the global arrival flags and agent-scope box accesses of lbvh_refit_kernel.  A lane that leaves the local
+// positions per window) take global arrival flags and agent-scope box accesses.  A lane that leaves the local
 // domain first publishes the box it carries (agent-scope store), then signs in at the parent's global flag like any other lane.
-// Same min / max merges in the same pairs: the boxes are bit-identical to the unwindowed kernel's (and the reference's, Bvh.hpp:469-492).
+// Same min / max merges in the same pairs: the boxes are bit-identical to an unwindowed walk's (and the reference's, Bvh.hpp:469-492).
 // A lane that leaves the local domain does not walk on inside this kernel (ten or twenty dependent agent-scope round trips would keep its
 // whole 1024-thread workgroup resident: measured, half of the kernel's time): it publishes its box and leaves the node in the window's
 // hand-over list (LBVH_RL entries per window; a full list falls back to walking here); lbvh_refit_upper_kernel continues from the lists.
@@ -745,19 +721,13 @@ static void lbvh_refit_impl(Launch &L, zs_rocm_lbvh &b, const AABB3 *primBvs) {
   }
   int *flags = (int *)L.temp(sizeof(int) * b.numNodes);
   ZSR_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * b.numNodes, L.stream));
-  static const bool plain = [] { const char *e = getenv("ZS_ROCM_LBVH_REFIT"); return e && e[0] == 'p'; }();  // A/B runs: the unwindowed kernel
-  if (plain)
-    hipLaunchKernelGGL(lbvh_refit_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, L.stream, n, primBvs, b.orderedBvs, b.auxIndices, b.leafInds,
-                       b.parents, b.levels, flags);
-  else {
-    constexpr int RW = 2048, RT = 1024;  // (1024 / 512: the same time; 2048 / 512 and 1024 / 1024: slower -- profiles/r04_lbvh.md)
-    const int nWindows = (int)ceil_div(b.numNodes, RW);
-    int *listCount = (int *)L.temp(sizeof(int) * nWindows), *list = (int *)L.temp(sizeof(int) * (size_t)nWindows * LBVH_RL);
-    hipLaunchKernelGGL((lbvh_refit_window_kernel<RW, RT>), dim3(nWindows), dim3(RT), 0, L.stream, (int)b.numNodes, primBvs, b.orderedBvs,
-                       b.auxIndices, b.parents, b.levels, flags, listCount, list);
-    hipLaunchKernelGGL(lbvh_refit_upper_kernel, dim3(ceil_div((size_t)nWindows * LBVH_RL, 256)), dim3(256), 0, L.stream, nWindows,
-                       (const int *)listCount, (const int *)list, b.orderedBvs, b.auxIndices, b.parents, b.levels, flags);
-  }
+  constexpr int RW = 2048, RT = 1024;  // (1024 / 512: the same time; 2048 / 512 and 1024 / 1024: slower -- profiles/r04_lbvh.md)
+  const int nWindows = (int)ceil_div(b.numNodes, RW);
+  int *listCount = (int *)L.temp(sizeof(int) * nWindows), *list = (int *)L.temp(sizeof(int) * (size_t)nWindows * LBVH_RL);
+  hipLaunchKernelGGL((lbvh_refit_window_kernel<RW, RT>), dim3(nWindows), dim3(RT), 0, L.stream, (int)b.numNodes, primBvs, b.orderedBvs,
+                     b.auxIndices, b.parents, b.levels, flags, listCount, list);
+  hipLaunchKernelGGL(lbvh_refit_upper_kernel, dim3(ceil_div((size_t)nWindows * LBVH_RL, 256)), dim3(256), 0, L.stream, nWindows,
+                     (const int *)listCount, (const int *)list, b.orderedBvs, b.auxIndices, b.parents, b.levels, flags);
 }
 
 }  // namespace zsr
@@ -842,14 +812,11 @@ void zs_rocm_lbvh_total_box(zs_rocm_policy *pol, const zs_rocm_lbvh *b, float *b
   hipLaunchKernelGGL(lbvh_box_reduce_kernel, dim3(1), dim3(BOX_BLOCK), 0, L.stream, b->orderedBvs, b->numLeaves, partial, 0);
   hipLaunchKernelGGL(lbvh_box_final_kernel, dim3(1), dim3(64), 0, L.stream, partial, 1, box6Dev);
 }
-#ifndef LBVH_QUERY_BLOCK
-#define LBVH_QUERY_BLOCK 256
-#endif
-// bulk iter_neighbors: >= 16384 queries are walked in Morton order of their centres (codes + one pair sort: ~0.1 ms per million);
-// ZS_ROCM_LBVH_QUERY=u keeps the caller's order (A/B runs).  nullptr: caller's order.
+constexpr int LBVH_QUERY_BLOCK = 256;
+// bulk iter_neighbors: >= 16384 queries are walked in Morton order of their centres (codes + one pair sort: ~0.1 ms per million).
+// nullptr: caller's order.
 static const int *lbvh_query_order(Launch &L, const zs_rocm_lbvh *b, const float *queryBvs, size_t nq) {
-  static const bool unsorted = [] { const char *e = getenv("ZS_ROCM_LBVH_QUERY"); return e && e[0] == 'u'; }();
-  if (unsorted || nq < 16384 || nq > 0x7fffffffu || b->numNodes <= 2) return nullptr;
+  if (nq < 16384 || nq > 0x7fffffffu || b->numNodes <= 2) return nullptr;
   unsigned *codes = (unsigned *)L.temp(sizeof(unsigned) * nq), *sorted = (unsigned *)L.temp(sizeof(unsigned) * nq);
   int *ids = (int *)L.temp(sizeof(int) * nq), *perm = (int *)L.temp(sizeof(int) * nq);
   hipLaunchKernelGGL(lbvh_query_code_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, L.stream, lbvh_packed(L, *b), (const AABB3 *)queryBvs, (int)nq,
@@ -875,9 +842,7 @@ void zs_rocm_lbvh_query_fill(zs_rocm_policy *pol, const zs_rocm_lbvh *b, const f
 }
 // one wave per workgroup: the walks of neighbouring waves differ in length, and a long one would keep the other wave slots of its
 // workgroup idle (count pass 2.97 -> 2.85 ms; 128 threads: 2.95)
-#ifndef LBVH_SELF_BLOCK
-#define LBVH_SELF_BLOCK 64
-#endif
+constexpr int LBVH_SELF_BLOCK = 64;
 void zs_rocm_lbvh_self_query_count(zs_rocm_policy *pol, const zs_rocm_lbvh *b, int *counts) {
   Launch L(pol, "lbvh_self_query_count");
   if (!b->numLeaves) return;
@@ -887,10 +852,8 @@ void zs_rocm_lbvh_self_query_count(zs_rocm_policy *pol, const zs_rocm_lbvh *b, i
     ZSR_CHECK(hipMalloc((void **)&b->hitCounts, b->numLeaves * sizeof(int)));
     b->hitCacheLeaves = b->numLeaves;
   }
-  // A/B runs: ZS_ROCM_LBVH_SELF=l selects the one-walk-per-leaf kernel of r03
-  static const bool perLeaf = [] { const char *e = getenv("ZS_ROCM_LBVH_SELF"); return e && e[0] == 'l'; }();
   // (the wave walk addresses nodes by a 32-bit byte offset, node << 5: trees of 2^27 nodes and more take the per-leaf kernel)
-  if (b->numNodes > 2 && b->numNodes < (1u << 27) && !perLeaf)
+  if (b->numNodes > 2 && b->numNodes < (1u << 27))
     hipLaunchKernelGGL((lbvh_self_query_wave_kernel<false>), dim3(ceil_div(b->numLeaves, LBVH_SELF_BLOCK)), dim3(LBVH_SELF_BLOCK), 0, L.stream, lbvh_packed(L, *b),
                        (int)b->numNodes, (int)b->numLeaves, (const int *)b->leafInds, counts, (const int *)nullptr, (int *)nullptr,
                        b->hitCache, b->hitCounts, 0);
@@ -903,8 +866,7 @@ void zs_rocm_lbvh_self_query_count(zs_rocm_policy *pol, const zs_rocm_lbvh *b, i
 void zs_rocm_lbvh_self_query_fill(zs_rocm_policy *pol, const zs_rocm_lbvh *b, const int *offsets, int *pairs) {
   Launch L(pol, "lbvh_self_query_fill");
   if (!b->numLeaves) return;
-  static const bool perLeaf = [] { const char *e = getenv("ZS_ROCM_LBVH_SELF"); return e && e[0] == 'l'; }();
-  if (b->numNodes > 2 && b->numNodes < (1u << 27) && !perLeaf)
+  if (b->numNodes > 2 && b->numNodes < (1u << 27))
     hipLaunchKernelGGL((lbvh_self_query_wave_kernel<true>), dim3(ceil_div(b->numLeaves, LBVH_SELF_BLOCK)), dim3(LBVH_SELF_BLOCK), 0, L.stream, lbvh_packed(L, *b),
                        (int)b->numNodes, (int)b->numLeaves, (const int *)b->leafInds, (int *)nullptr, offsets, pairs, b->hitCache, b->hitCounts,
                        b->hitCacheValid ? 1 : 0);

@@ -22,9 +22,7 @@ using namespace zsr;
 namespace {
 
 constexpr int C2_TRANSFER = 0, C2_MOMENTUM = 1, C2_FORCE = 2;
-#ifndef ZS_C2_CXN
-#  define ZS_C2_CXN 2  // 2 x 2 x 2 cells per lane (1: 1 x 2 x 2 -- measured 5 % slower)
-#endif
+constexpr int C2_CXN = 2;  // 2 x 2 x 2 cells per lane (1: 1 x 2 x 2 -- measured 5 % slower)
 
 __device__ __forceinline__ float c2_dinv(float x, float dx, float dxi) {
   const float r = x - (float)(int)floorf(x * dxi + 0.5f) * dx;  // P2C2G.hpp:88
@@ -141,90 +139,12 @@ template <int SIDE> __device__ __forceinline__ int c2_bucket_no(const C2Buckets 
   return b < 0 ? -1 : b * (SIDE * SIDE * SIDE) + (loc[0] * SIDE + loc[1]) * SIDE + loc[2];
 }
 
-// ---- P2C2G stage 2: per cell, the 16 moments m_c, mv_c, Q_c, (Q x_p)_c  (P2C2G.hpp:66-163); sums[b][16][NC].  One workgroup per
-// block: the bucket ranges of the (SIDE+2)^3 cells around the block are looked up once (one hash probe per halo cell instead of 27 per
-// cell) and kept in LDS together with the octant offsets of stage 0.
-template <int SIDE, int KIND>
-__global__ __launch_bounds__(256) void p2c2g_cell_kernel(MpmDev mp, BhtDev t, C2Buckets buckets, const int *offsets,
-                                                         const unsigned long long *sub, const float4 *rec, float *sums) {
-  constexpr int NC = SIDE * SIDE * SIDE, H = SIDE + 2, NH = H * H * H;
-  __shared__ int2 range[NH];
-  __shared__ unsigned long long octs[NH];
-  const int b = blockIdx.x;
-  const float dx = mp.dx, dxi = mp.dxi;
-  int org[3];
-  c2_cell_coord<SIDE>(t, b, 0, mp.kscale, org);
-  for (int h = threadIdx.x; h < NH; h += blockDim.x) {
-    const int bc[3] = {org[0] - 1 + h / (H * H), org[1] - 1 + (h / H) % H, org[2] - 1 + h % H};
-    const int bno = c2_bucket_no<SIDE>(buckets, t, mp.kscale, bc);
-    range[h] = bno < 0 ? make_int2(0, 0) : make_int2(offsets[bno], offsets[bno + 1] - offsets[bno]);  // {start, count}
-    octs[h] = bno < 0 ? 0ull : sub[bno];
-  }
-  __syncthreads();
-  for (int cell = threadIdx.x; cell < NC; cell += blockDim.x) {
-    const int lx = cell / (SIDE * SIDE), ly = (cell / SIDE) % SIDE, lz = cell % SIDE;
-    const float pc0 = ((float)(org[0] + lx) + 0.5f) * dx, pc1 = ((float)(org[1] + ly) + 0.5f) * dx, pc2 = ((float)(org[2] + lz) + 0.5f) * dx;
-    float m_c = 0.f, mv[3] = {0.f, 0.f, 0.f}, Qc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, QX[3] = {0.f, 0.f, 0.f};
-    for (int o = 0; o < 27; ++o) {  // ndrange<3>(3) order
-      const int ox = o / 9, oy = (o / 3) % 3, oz = o % 3;
-      const int h = ((lx + ox) * H + ly + oy) * H + lz + oz;
-      const int2 sc = range[h];
-      if (!sc.y) continue;
-      const unsigned long long oc = octs[h];
-      const bool ordered = oc != ~0ull;
-      // half-cells of the bucket that can reach this cell: offset -1 -> upper half only, +1 -> lower half only
-      const int xlo = ox == 0, xhi = ox != 2, ylo = oy == 0, yhi = oy != 2, zlo = oz == 0, zhi = oz != 2;
-      for (int hx = xlo; hx <= xhi; ++hx)
-        for (int hy = ylo; hy <= yhi; ++hy) {
-          int a = 0, e = sc.y;
-          if (ordered) {
-            const int clo = hx * 4 + hy * 2 + zlo, chi = hx * 4 + hy * 2 + zhi;
-            a = (int)((oc >> (8 * clo)) & 255);
-            if (chi != 7) e = (int)((oc >> (8 * chi + 8)) & 255);
-          } else if (hx != xlo || hy != ylo) {
-            continue;  // an unordered bucket is walked once, whole
-          }
-          for (int st = sc.x + a, ed = sc.x + e; st < ed; ++st) {
-            const float4 *r = rec + 4 * (size_t)st;
-            const float4 r0 = r[0];
-            const float d0 = pc0 - r0.x, d1 = pc1 - r0.y, d2 = pc2 - r0.z;
-            if (fabsf(d0) > dx || fabsf(d1) > dx || fabsf(d2) > dx) continue;  // checkInKernelRange, :72-76
-            const float4 r1 = r[1], r2 = r[2], r3 = r[3];
-            const float a0 = fabsf(d0 * dxi), a1 = fabsf(d1 * dxi), a2 = fabsf(d2 * dxi);
-            float W = 1.f;
-            if constexpr (KIND == C2_TRANSFER) {  // :149-151
-              W *= 1.f - a0; W *= 1.f - a1; W *= 1.f - a2;
-            } else {  // :396-402, :649-655
-              W *= a0 <= 1 ? 1.f - a0 : 0.f; W *= a1 <= 1 ? 1.f - a1 : 0.f; W *= a2 <= 1 ? 1.f - a2 : 0.f;
-            }
-            const float Q[9] = {r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x};
-            // all 16 moments for every kind (the Force variant's node stage ignores m_c, mv_c): when that variant read only part of
-            // the record the compiler re-sliced the four float4 loads into 16-byte loads at offsets 12 / 28 plus a late dependent
-            // dword, and the kernel ran 2x slower than the variants that use everything
-            m_c += r0.w * W;
-            mv[0] += r3.y * W; mv[1] += r3.z * W; mv[2] += r3.w * W;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) QX[d] += (Q[d] * r0.x + Q[3 + d] * r0.y + Q[6 + d] * r0.z) * W;
-#pragma unroll
-            for (int d = 0; d < 9; ++d) Qc[d] += Q[d] * W;
-          }
-        }
-    }
-    float *s = sums + (size_t)b * 16 * NC + cell;
-    s[0] = m_c;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) s[(1 + d) * NC] = mv[d];
-#pragma unroll
-    for (int d = 0; d < 9; ++d) s[(4 + d) * NC] = Qc[d];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) s[(13 + d) * NC] = QX[d];
-  }
-}
-
-// ---- P2C2G stage 2, 2x2x2 cells per lane: the 8 cells of a lane need the particles of a 3x3x3-cell volume (27 x 8 records instead of
-// 8 x 64: the cell-per-lane kernel above leaves L2 with 8-16 GB per launch because the 8 cells that need a record run at different
-// times in different waves).  The record is loaded once and applied to whichever of the lane's 8 cells it is in range of.  One wave per
-// 8^3 block (8 blocks of 4^3 cells per wave).
+// ---- P2C2G stage 2: per cell, the 16 moments m_c, mv_c, Q_c, (Q x_p)_c  (P2C2G.hpp:66-163); sums[b][16][NC].  The bucket ranges of the
+// (SIDE+2)^3 cells around a block are looked up once (one hash probe per halo cell instead of 27 per cell) and kept in LDS together with
+// the octant offsets of stage 0.  CXN x 2 x 2 cells per lane: the 8 cells of a lane need the particles of a 3x3x3-cell volume (27 x 8
+// records instead of 8 x 64: a cell-per-lane kernel leaves L2 with 8-16 GB per launch because the 8 cells that need a record run at
+// different times in different waves).  The record is loaded once and applied to whichever of the lane's 8 cells it is in range of.
+// One wave per 8^3 block (8 blocks of 4^3 cells per wave).
 template <int SIDE, int KIND, int CXN>
 __global__ __launch_bounds__(128) void p2c2g_cell8_kernel(MpmDev mp, BhtDev t, C2Buckets buckets, const int *offsets,
                                                          const unsigned long long *sub, const float4 *rec, float *sums, int nblocks) {
@@ -541,16 +461,10 @@ int zs_rocm_mpm_p2c2g(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_
                                                 (const int *)slotOf, rec);
   else { ZSR_DISPATCH_PURE_(0, p->model, CALL_C2_PARTICLE) }
   const C2Buckets bk{buckets->dense ? HtDev{} : buckets->table->dev(), buckets->dense};
-  static const bool cell1 = [] { const char *e = getenv("ZS_ROCM_C2_CELL1"); return e && e[0] == '1'; }();  // the cell-per-lane kernel
-  constexpr int CXN = ZS_C2_CXN;  // cells per lane = CXN x 2 x 2
 #define CALL_C2_CELLS(S, K)                                                                                                               \
-  if (cell1)                                                                                                                              \
-    hipLaunchKernelGGL((p2c2g_cell_kernel<S, K>), dim3((unsigned)nblocks), dim3(S == 4 ? 64 : 256), 0, L.stream, mp, t, bk,                \
-                       (const int *)buckets->offsets, (const unsigned long long *)sub, (const float4 *)rec, sums);                        \
-  else                                                                                                                                    \
-    hipLaunchKernelGGL((p2c2g_cell8_kernel<S, K, CXN>), dim3((unsigned)ceil_div(nblocks, (size_t)(S == 4 ? 4 * CXN : 1))),                \
-                       dim3(S == 4 ? 64 : 128 / CXN), 0, L.stream, mp, t, bk, (const int *)buckets->offsets,                              \
-                       (const unsigned long long *)sub, (const float4 *)rec, sums, (int)nblocks);                                         \
+  hipLaunchKernelGGL((p2c2g_cell8_kernel<S, K, C2_CXN>), dim3((unsigned)ceil_div(nblocks, (size_t)(S == 4 ? 4 * C2_CXN : 1))),            \
+                     dim3(S == 4 ? 64 : 128 / C2_CXN), 0, L.stream, mp, t, bk, (const int *)buckets->offsets,                                \
+                     (const unsigned long long *)sub, (const float4 *)rec, sums, (int)nblocks);                                           \
   hipLaunchKernelGGL((p2c2g_node_kernel<S, K>), dim3((unsigned)nblocks), dim3(S == 4 ? 64 : 256), 0, L.stream, mp, t, (const float *)sums, grid)
 #define CALL_C2_KIND(S)                                    \
   if (kind == C2_TRANSFER) { CALL_C2_CELLS(S, C2_TRANSFER); } \

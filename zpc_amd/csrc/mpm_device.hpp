@@ -544,27 +544,23 @@ template <int LW> __device__ __forceinline__ float pload1(const Port<float> &p, 
   if constexpr (LW != 0) return p.base[o.o + comp * LW];
   else return p.base[p.off(o.o) + comp * p.cstride()];
 }
-template <int LW, int N> __device__ __forceinline__ void pstore(const Port<float> &p, POff<LW> o, const float (&v)[N]) {
+// NT: tiled particle state written with non-temporal stores (see g2p_packed_kernel)
+template <int LW, int N, bool NT = false> __device__ __forceinline__ void pstore(const Port<float> &p, POff<LW> o, const float (&v)[N]) {
   if constexpr (LW != 0) {
     float *b = p.base + o.o;
 #pragma unroll
     for (int d = 0; d < N; ++d) {
-#ifdef ZS_PSTORE_NT  // measurement builds: particle state written with non-temporal stores
-      __builtin_nontemporal_store(v[d], b + d * LW);
-#else
-      b[d * LW] = v[d];
-#endif
+      if constexpr (NT) __builtin_nontemporal_store(v[d], b + d * LW);
+      else b[d * LW] = v[d];
     }
   } else
     store_attr<N>(p, o.o, v);
 }
-template <int LW> __device__ __forceinline__ void pstore1(const Port<float> &p, POff<LW> o, float v) {
-#ifdef ZS_PSTORE_NT
-  if constexpr (LW != 0) __builtin_nontemporal_store(v, p.base + o.o);
-#else
-  if constexpr (LW != 0) p.base[o.o] = v;
-#endif
-  else p.base[p.off(o.o)] = v;
+template <int LW, bool NT = false> __device__ __forceinline__ void pstore1(const Port<float> &p, POff<LW> o, float v) {
+  if constexpr (LW != 0) {
+    if constexpr (NT) __builtin_nontemporal_store(v, p.base + o.o);
+    else p.base[o.o] = v;
+  } else p.base[p.off(o.o)] = v;
 }
 // deformation state of a particle: F (9 components) for the solids, the volume ratio J = component 0 of the same attribute
 // for the EquationOfState fluid (Structurefree.hpp: particles.F / particles.J)
@@ -576,9 +572,9 @@ template <int LW, bool FLUID> __device__ __forceinline__ void pload_state(const 
   } else
     pload<LW, 9>(p, o, F);
 }
-template <int LW, bool FLUID> __device__ __forceinline__ void pstore_state(const Port<float> &p, POff<LW> o, const float (&F)[9]) {
-  if constexpr (FLUID) pstore1<LW>(p, o, F[0]);
-  else pstore<LW, 9>(p, o, F);
+template <int LW, bool FLUID, bool NT = false> __device__ __forceinline__ void pstore_state(const Port<float> &p, POff<LW> o, const float (&F)[9]) {
+  if constexpr (FLUID) pstore1<LW, NT>(p, o, F[0]);
+  else pstore<LW, 9, NT>(p, o, F);
 }
 template <bool FLUID> __device__ __forceinline__ void load_state(const Port<float> &p, size_t i, float (&F)[9]) {
   if constexpr (FLUID) {
@@ -768,17 +764,7 @@ static __global__ __launch_bounds__(256) void build_neighbors_kernel(BhtDev t, i
 // dispatcher deals workgroups round-robin over the 8 XCDs -- changes neither the atomics' write traffic, which is write-through per
 // touched 32-byte sector whatever the order, nor the time for the better: the empty apron bins end up on a few XCDs and the
 // stand-alone P2G runs 1.83 -> 2.09 ms, the slotted step 7.9 -> 11.3 ms; numbering the blocks lexicographically or along the Morton
-// curve instead of in insertion order: 1.86 / 1.91 ms and 8.5 / 8.2 ms.  profiles/r04_launch_order.md.  -DZS_ROCM_XCD_CHUNKS keeps
-// the mapping for measurement builds.)
-__device__ __forceinline__ unsigned xcd_chunked(unsigned i, unsigned n) {
-#ifdef ZS_ROCM_XCD_CHUNKS
-  const unsigned q = n >> 3, rem = n & 7u, k = i & 7u, j = i >> 3;
-  return k * q + (k < rem ? k : rem) + j;
-#else
-  (void)n;
-  return i;
-#endif
-}
+// curve instead of in insertion order: 1.86 / 1.91 ms and 8.5 / 8.2 ms.  profiles/r04_launch_order.md.)
 
 template <int SIDE> constexpr int bins_per_block() { return (SIDE / 4) * (SIDE / 4) * (SIDE / 4); }
 
@@ -1026,7 +1012,7 @@ static __global__ __launch_bounds__(64, 2) void p2g_binned_kernel(MpmDev mp, Par
   using AL = ArenaLds;
   constexpr int NC = SIDE * SIDE * SIDE;
   __shared__ float arena[7 * AL::CH];
-  const int bin = (int)xcd_chunked(blockIdx.x, gridDim.x);
+  const int bin = (int)blockIdx.x;
   const int start = binStart[bin], end = binStart[bin + 1];
   if (start == end) return;  // empty bin (ghost block): uniform exit
   const int lane = threadIdx.x;
@@ -1219,9 +1205,6 @@ constexpr int P2GW_MQ_CAP = 256;  // in-bin movers the wide P2G takes through it
 // `tileBase`: wave-uniform element offset of a tile at or before the bin's first particle.  The per-lane part of every address
 // is then a 32-bit byte offset from a scalar base (global_load_lds_dword v_off, s[base:base+1] offset:imm): ONE address VGPR
 // per round instead of a 64-bit pointer per attribute.
-#ifndef ZS_P2GW_AUX
-#define ZS_P2GW_AUX 0  // cache-policy bits of the record loads (measurement builds: 2 = nt)
-#endif
 template <int LW>
 __device__ __forceinline__ void p2gw_issue(const ParticlesDev &ps, size_t i, bool has, float *buf, size_t tileBase) {
   // every lane of the wave executes the 25 instructions (LDS destination = wave-uniform row + lane * 4); lanes without a
@@ -1235,15 +1218,15 @@ __device__ __forceinline__ void p2gw_issue(const ParticlesDev &ps, size_t i, boo
       else
         return p.base + p.off(o.o) + (size_t)comp * p.cstride();
     };
-    __builtin_amdgcn_global_load_lds(ptr(ps.mass, 0), (__attribute__((address_space(3))) void *)(buf + 0 * 64), 4, 0, ZS_P2GW_AUX);
+    __builtin_amdgcn_global_load_lds(ptr(ps.mass, 0), (__attribute__((address_space(3))) void *)(buf + 0 * 64), 4, 0, 0);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) __builtin_amdgcn_global_load_lds(ptr(ps.pos, d), (__attribute__((address_space(3))) void *)(buf + (1 + d) * 64), 4, 0, ZS_P2GW_AUX);
+    for (int d = 0; d < 3; ++d) __builtin_amdgcn_global_load_lds(ptr(ps.pos, d), (__attribute__((address_space(3))) void *)(buf + (1 + d) * 64), 4, 0, 0);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) __builtin_amdgcn_global_load_lds(ptr(ps.vel, d), (__attribute__((address_space(3))) void *)(buf + (4 + d) * 64), 4, 0, ZS_P2GW_AUX);
+    for (int d = 0; d < 3; ++d) __builtin_amdgcn_global_load_lds(ptr(ps.vel, d), (__attribute__((address_space(3))) void *)(buf + (4 + d) * 64), 4, 0, 0);
 #pragma unroll
-    for (int d = 0; d < 9; ++d) __builtin_amdgcn_global_load_lds(ptr(ps.C, d), (__attribute__((address_space(3))) void *)(buf + (7 + d) * 64), 4, 0, ZS_P2GW_AUX);
+    for (int d = 0; d < 9; ++d) __builtin_amdgcn_global_load_lds(ptr(ps.C, d), (__attribute__((address_space(3))) void *)(buf + (7 + d) * 64), 4, 0, 0);
 #pragma unroll
-    for (int d = 0; d < STRESS_N; ++d) __builtin_amdgcn_global_load_lds(ptr(ps.stress, d), (__attribute__((address_space(3))) void *)(buf + (16 + d) * 64), 4, 0, ZS_P2GW_AUX);
+    for (int d = 0; d < STRESS_N; ++d) __builtin_amdgcn_global_load_lds(ptr(ps.stress, d), (__attribute__((address_space(3))) void *)(buf + (16 + d) * 64), 4, 0, 0);
   }
 }
 template <int LW> __device__ __forceinline__ size_t p2gw_tile_base(const ParticlesDev &ps, int start) {
@@ -1304,8 +1287,8 @@ __device__ __forceinline__ void p2gw_accumulate(const MpmDev &mp, const Arena &a
 }
 
 // LDS arena shared by the G bins of one workgroup of p2g_wide_kernel: G = 1 one bin (6^3 nodes, ArenaLds), G = 2 the two bins of a
-// block that are neighbours in z (4 x 4 x 8 cells, 6 x 6 x 10 nodes), G = 4 the four bins of a half block (4 x 8 x 8 cells, 6 x 10 x 10
-// nodes).  Strides from a search over (SY, SX): for a fixed stencil offset the 64 cells of a bin land on 32 distinct banks per half wave.
+// block that are neighbours in z (4 x 4 x 8 cells, 6 x 6 x 10 nodes).  Strides from a search over (SY, SX): for a fixed stencil offset
+// the 64 cells of a bin land on 32 distinct banks per half wave.
 template <int G> struct ArenaLdsG;
 template <> struct ArenaLdsG<1> {
   static constexpr int WX = 6, WY = 6, WZ = 6, SY = ArenaLds::SY, SX = ArenaLds::SX, CH = WX * SX;
@@ -1315,16 +1298,12 @@ template <> struct ArenaLdsG<2> {
   static constexpr int WX = 6, WY = 6, WZ = 10, SY = 12, SX = 80, CH = WX * SX;
   __device__ static constexpr int at(int x, int y, int z) { return x * SX + y * SY + z; }
 };
-template <> struct ArenaLdsG<4> {
-  static constexpr int WX = 6, WY = 10, WZ = 10, SY = 12, SX = 144, CH = WX * SX;
-  __device__ static constexpr int at(int x, int y, int z) { return x * SX + y * SY + z; }
-};
 
 // tail shared by the wide P2G kernels: the queued in-bin movers go into the arena by LDS atomics (same values as the exact path), then
 // the arena goes to the grid -- origin of the workgroup's arena inside its block = the origin of its first bin
 template <int SIDE, int G>
 __device__ __forceinline__ void p2gw_movers_and_flush(const MpmDev &mp, const ParticlesDev &ps, const BinGeom<SIDE> &geo, float *arena, const int *mqw,
-                                                      int mqCountW, int lane, int ay, int az, const int *nbr, float *grid) {
+                                                      int mqCountW, int lane, int az, const int *nbr, float *grid) {
   using AL = ArenaLdsG<G>;
   constexpr int NC = SIDE * SIDE * SIDE;
   const float kscale = mp.fscale;
@@ -1346,7 +1325,7 @@ __device__ __forceinline__ void p2gw_movers_and_flush(const MpmDev &mp, const Pa
       for (int d = 0; d < 9; ++d) PF[d] *= kscale;
       Arena ar;
       make_arena(mp.dx, mp.dxi, pos, ar);
-      float *b0 = arena + AL::at(ar.corner[0] - geo.org[0], ar.corner[1] - geo.org[1] + ay, ar.corner[2] - geo.org[2] + az);
+      float *b0 = arena + AL::at(ar.corner[0] - geo.org[0], ar.corner[1] - geo.org[1], ar.corner[2] - geo.org[2] + az);
 #pragma unroll
       for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -1367,7 +1346,7 @@ __device__ __forceinline__ void p2gw_movers_and_flush(const MpmDev &mp, const Pa
     __syncthreads();
   }
   // flush: origin of the workgroup's arena inside its block = the origin of its first bin
-  const int o0[3] = {geo.o[0], geo.o[1] - ay, geo.o[2] - az};
+  const int o0[3] = {geo.o[0], geo.o[1], geo.o[2] - az};
   for (int node = threadIdx.x; node < AL::WX * AL::WY * AL::WZ; node += 64 * G) {
     const int x = node / (AL::WY * AL::WZ), y = (node / AL::WZ) % AL::WY, z = node % AL::WZ;
     int slot2, cell;
@@ -1385,14 +1364,6 @@ __device__ __forceinline__ void p2gw_movers_and_flush(const MpmDev &mp, const Pa
   }
 }
 
-#ifdef ZS_PROBE_P2G  // measurement-only build (tools/ab_build.sh): s_memtime stamps of a wave's phases in p2g_wide_kernel, summed over the sampled waves
-__device__ unsigned long long g_p2g_probe[16];
-#define P2G_NOW() ((unsigned long long)__builtin_readcyclecounter())
-#define P2G_STAMP(slot, dt) do { if (pSample) atomicAdd(&g_p2g_probe[slot], (unsigned long long)(dt)); } while (0)
-#else
-#define P2G_NOW() 0ull
-#define P2G_STAMP(slot, dt) do { } while (0)
-#endif
 // DEPTH = rounds of records in flight ahead of the one being computed (DEPTH + 1 LDS buffers of P2GW_NF x 256 B per wave).
 // G = bins (= waves) per workgroup.  Every wave streams its own bin exactly as a one-wave workgroup would (nothing is shared while the
 // records flow); what the G waves share is the flush: their register stencils go into ONE arena and the workgroup issues one set of
@@ -1403,7 +1374,7 @@ __device__ unsigned long long g_p2g_probe[16];
 template <int SIDE, int LW, int DEPTH, int G>
 static __global__ __launch_bounds__(64 * G, 2) void p2g_wide_kernel(MpmDev mp, ParticlesDev ps, BhtDev t, float *grid, const int *binStart,
                                                            const unsigned *cellCount, const int *nbr, int *stale, int *staleCount) {
-  static_assert(G == 1 || (SIDE == 8 && (G == 2 || G == 4)), "G bins of one block");
+  static_assert(G == 1 || (SIDE == 8 && G == 2), "G bins of one block");
   using AL = ArenaLdsG<G>;
   constexpr int NC = SIDE * SIDE * SIDE;
   constexpr int NB = DEPTH + 1;
@@ -1414,12 +1385,7 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_wide_kernel(MpmDev mp, P
   __shared__ int mq[G][P2GW_MQ_CAP];  // particles that sit in another cell of their bin (moved since the last re-bin)
   __shared__ int mqCount[G];
   const int w = G == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;  // (w in an SGPR)
-  const int bin0 = (int)xcd_chunked(blockIdx.x, gridDim.x) * G, bin = bin0 + w;
-#ifdef ZS_PROBE_P2G
-  const bool pSample = lane == 0 && (blockIdx.x & 15) == 0;
-  const unsigned long long tp0 = P2G_NOW();
-  unsigned long long tpWait = 0, tpRounds = 0;
-#endif
+  const int bin0 = (int)blockIdx.x * G, bin = bin0 + w;
   if (binStart[bin0] == binStart[bin0 + G]) return;  // none of the G bins holds a particle (workgroup-uniform)
   float *arena = lds;
   float(*pbuf)[P2GW_NF * 64] = reinterpret_cast<float(*)[P2GW_NF * 64]>(lds + w * WBUF);
@@ -1456,9 +1422,6 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_wide_kernel(MpmDev mp, P
   int i0;
   bool any;
   bool has0 = walk.next(i0, any);
-#ifdef ZS_PROBE_P2G
-  const unsigned long long tp1 = P2G_NOW();  // head done: counts known, first DEPTH rounds requested
-#endif
   while (any) {
     if (lany) {
       const bool lh = lead.next(li, lany);
@@ -1471,16 +1434,9 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_wide_kernel(MpmDev mp, P
     // wait until only the records issued AFTER the current one are still in flight
     // (a record is P2GW_NF loads; vmcnt holds 6 bits: two records in flight is the most that can be told apart)
     static_assert(2 * P2GW_NF <= 63, "vmcnt range");
-#ifdef ZS_PROBE_P2G
-    const unsigned long long tw0 = P2G_NOW();
-#endif
     if (issued >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P2GW_NF) : "memory");
     else if (issued == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P2GW_NF) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ZS_PROBE_P2G
-    tpWait += P2G_NOW() - tw0;
-    ++tpRounds;
-#endif
     if (has0) {
       const float *rec = pbuf[slot] + lane;
       const float pos[3] = {rec[1 * 64], rec[2 * 64], rec[3 * 64]};
@@ -1506,18 +1462,12 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_wide_kernel(MpmDev mp, P
     slot = slot + 1 == NB ? 0 : slot + 1;
     has0 = walk.next(i0, any);
   }
-#ifdef ZS_PROBE_P2G
-  const unsigned long long tp2 = P2G_NOW();  // stream done
-#endif
   __syncthreads();  // every record of every wave has been consumed: the region becomes the arena
   for (int k = threadIdx.x; k < 7 * AL::CH; k += 64 * G) arena[k] = 0.f;
   __syncthreads();
-#ifdef ZS_PROBE_P2G
-  const unsigned long long tp3 = P2G_NOW();  // waited for the other waves, arena cleared
-#endif
-  // this bin's corner inside the workgroup's arena: the G bins differ in z (G = 2) or in y and z (G = 4)
-  const int ay = G == 4 ? (w >> 1) * 4 : 0, az = G == 1 ? 0 : (w & 1) * 4;
-  float *a0 = arena + AL::at(cx, cy + ay, cz + az);
+  // this bin's corner inside the workgroup's arena: the G = 2 bins differ in z
+  const int az = G == 1 ? 0 : (w & 1) * 4;
+  float *a0 = arena + AL::at(cx, cy, cz + az);
 #pragma unroll
   for (int k = 0; k < 27; ++k) {  // 27 conflict-free phases: in a phase the 64 G lanes of the workgroup own 64 G distinct nodes
     float *g = a0 + AL::at(k / 9, (k / 3) % 3, k % 3);
@@ -1527,27 +1477,7 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_wide_kernel(MpmDev mp, P
     else __syncthreads();
   }
   __syncthreads();
-#ifdef ZS_PROBE_P2G
-  const unsigned long long tp4 = P2G_NOW();  // 27 phases done
-#endif
-  p2gw_movers_and_flush<SIDE, G>(mp, ps, geo, arena, mq[w], mqCount[w], lane, ay, az, nbr, grid);
-#ifdef ZS_PROBE_P2G
-  {
-    const unsigned long long tp5 = P2G_NOW();  // atomics issued
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long tp6 = P2G_NOW();
-    P2G_STAMP(0, tp6 - tp0);   // life of the wave
-    P2G_STAMP(1, tp1 - tp0);   // head: bin range, cell counts, block key, first requests
-    P2G_STAMP(2, tp2 - tp1);   // record stream (all rounds)
-    P2G_STAMP(3, tpWait);      // ... of which inside s_waitcnt vmcnt
-    P2G_STAMP(4, tp3 - tp2);   // barrier with the group's other waves + arena clear
-    P2G_STAMP(5, tp4 - tp3);   // 27 register -> arena phases
-    P2G_STAMP(6, tp5 - tp4);   // movers' post-pass + arena -> grid atomics issued
-    P2G_STAMP(7, tp6 - tp5);   // atomics drained
-    P2G_STAMP(8, 1);           // sampled waves
-    P2G_STAMP(9, tpRounds);    // rounds
-  }
-#endif
+  p2gw_movers_and_flush<SIDE, G>(mp, ps, geo, arena, mq[w], mqCount[w], lane, az, nbr, grid);
 }
 
 // The lane's 27 x 7 node sums of p2g_tile_kernel with the six vector channels as three register PAIRS per node, {mv_x, mv_y},
@@ -1732,7 +1662,7 @@ __device__ __forceinline__ void p2gt_issue(const ParticlesDev &ps, int tile, int
 template <int SIDE, int NB, int G, bool MERGED>
 static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, ParticlesDev ps, BhtDev t, float *grid, const int *binStart,
                                                            const unsigned *cellCount, const int *nbr, int *stale, int *staleCount) {
-  static_assert(G == 1 || (SIDE == 8 && (G == 2 || G == 4)), "G bins of one block");
+  static_assert(G == 1 || (SIDE == 8 && G == 2), "G bins of one block");
   constexpr int NL = p2gt_requests<MERGED>();  // load instructions per tile
   static_assert((NB - 1) * NL <= 63, "vmcnt range");
   using AL = ArenaLdsG<G>;
@@ -1745,12 +1675,7 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
   __shared__ int mqCount[G];
   __shared__ unsigned cntLds[G][64];
   const int w = G == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const int bin0 = (int)xcd_chunked(blockIdx.x, gridDim.x) * G, bin = bin0 + w;
-#ifdef ZS_PROBE_P2G
-  const bool pSample = lane == 0 && (blockIdx.x & 15) == 0;
-  const unsigned long long tp0 = P2G_NOW();
-  unsigned long long tpWait = 0, tpRounds = 0;
-#endif
+  const int bin0 = (int)blockIdx.x * G, bin = bin0 + w;
   // the G + 1 range words of the workgroup's bins and this wave's cell counts are requested together
   int bs[G + 1];
 #pragma unroll
@@ -1799,23 +1724,12 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
   for (int k = 0; k < 8; ++k)  // (constant address space + uniform address = s_load: vmcnt stays the record requests' own)
     nbs[k] = reinterpret_cast<const __attribute__((address_space(4))) int *>(reinterpret_cast<unsigned long long>(nbr))[(size_t)geo.block * 8 + k];
   const float kscale = mp.fscale;  // contrib = -dt D_inv (P F^T vol)
-#ifdef ZS_P2GT_SCALAR  // measurement builds: the scalar accumulation of p2g_wide_kernel
-  struct { float a[27][7]; __device__ __forceinline__ float get(int k, int ch) const { return a[k][ch]; } } acc;
-#pragma unroll
-  for (int k = 0; k < 27; ++k)
-#pragma unroll
-    for (int ch = 0; ch < 7; ++ch) acc.a[k][ch] = 0.f;
-#else
   P2GAccPk acc;
   acc.clear();
-#endif
   int base = start;      // first particle of the round (wave-uniform)
   int tDone = tile0;     // tiles below have arrived
   int cslot = 0;         // ring slot of tile base / 64
   unsigned r = 0;
-#ifdef ZS_PROBE_P2G
-  const unsigned long long tp1 = P2G_NOW();
-#endif
   {  // the cell counts were requested before the first tiles: they have arrived once at most the tiles' requests are outstanding
     const int req = tIssue - tile0;
     if (req >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB >= 3 ? 3 * NL : 0) : "memory");
@@ -1832,12 +1746,6 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
     const int tb = base >> 6, tLast = (base + nr - 1) >> 6;
     // a tile buffer is free once the walk has passed the tile: tile tIssue - NB was left when base reached (tIssue - NB + 1) * 64
     if (tIssue < tileEnd && tb > tIssue - NB) request();
-#ifdef ZS_P2GT_LOOPSYNC
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-#ifdef ZS_PROBE_P2G
-    const unsigned long long tw0 = P2G_NOW();
-#endif
     if (tLast >= tDone) {
       const int ahead = tIssue - 1 - tLast;  // requested tiles the round does not need yet
       if (NB >= 4 && ahead >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB >= 4 ? 3 * NL : 0) : "memory");
@@ -1846,10 +1754,6 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       tDone = tLast + 1;
     }
-#ifdef ZS_PROBE_P2G
-    tpWait += P2G_NOW() - tw0;
-    ++tpRounds;
-#endif
     {
       // every lane reads "its" record (a lane without a particle in this round reads some record of the ring: never used) so that the
       // round has ONE divergent region, the accumulation; movers are rare and sit behind a wave-uniform branch
@@ -1861,11 +1765,7 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
       const int ocx = ar.corner[0] - geo.org[0], ocy = ar.corner[1] - geo.org[1], ocz = ar.corner[2] - geo.org[2];
       const bool inBin = (unsigned)(ocx | ocy | ocz) < 4u;  // all three in 0..3
       const bool own = has && inBin && ((ocx << 4) | (ocy << 2) | ocz) == lane;  // lane = cell: (x, y, z) = (lane >> 4, (lane >> 2) & 3, lane & 3)
-#ifdef ZS_P2GT_SCALAR
-      if (own) p2gw_accumulate(mp, ar, rec, kscale, acc.a);
-#else
       p2gw_accumulate_pk(mp, ar, rec, kscale, own, acc);
-#endif
       if (__ballot(has && !own) != 0ull) {  // some particle has left the cell it is stored under (wave-uniform, rare)
         if (has && !own) {
           bool queued = false;
@@ -1886,9 +1786,6 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
     has = cnt > r;
     m = __ballot(has);
   }
-#ifdef ZS_PROBE_P2G
-  const unsigned long long tp2 = P2G_NOW();
-#endif
   // ---- tail.  Every tile the wave requested has been consumed, so its ring is free: it becomes the wave's PRIVATE 6^3 arena, two
   // planes of one float4 per node ({m, mv} and {f, -}: ArenaPriv).  No other wave touches it until the group's barrier below, and a
   // wave's LDS operations execute in order, so the 27 read-add-write phases need no barrier and no wait for a write: the 16-byte read
@@ -1903,9 +1800,6 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
     __builtin_amdgcn_wave_barrier();                       \
   } while (0)
   P2GT_LDS_ORDER();
-#ifdef ZS_PROBE_P2G
-  const unsigned long long tp3 = P2G_NOW();
-#endif
   {
     float4 *a0 = priv + AP::at(lane >> 4, (lane >> 2) & 3, lane & 3);
     float4 va = a0[0], vb = a0[AP::PLANE];
@@ -1961,14 +1855,11 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
   if constexpr (G == 1) P2GT_LDS_ORDER();
   else __syncthreads();  // the G private arenas are complete
 #undef P2GT_LDS_ORDER
-#ifdef ZS_PROBE_P2G
-  const unsigned long long tp4 = P2G_NOW();
-#endif
-  // flush.  The group's nodes (6 x 6 x 6 G: the bins differ in z (G = 2) or in y and z (G = 4)) go to the grid once each: an apron
-  // node between two (four) bins is the sum of what their private arenas hold for it.
+  // flush.  The group's nodes (6 x 6 x 6 G: the G = 2 bins differ in z) go to the grid once each: an apron node between two bins is
+  // the sum of what their private arenas hold for it.
   {
-    const int wy = G == 4 ? (w >> 1) * 4 : 0, wz = G == 1 ? 0 : (w & 1) * 4;
-    const int o0[3] = {geo.o[0], geo.o[1] - wy, geo.o[2] - wz};  // origin of the group inside its block = the origin of its first bin
+    const int wz = G == 1 ? 0 : (w & 1) * 4;
+    const int o0[3] = {geo.o[0], geo.o[1], geo.o[2] - wz};  // origin of the group inside its block = the origin of its first bin
     constexpr int NODES = AL::WX * AL::WY * AL::WZ, ITER = (NODES + 64 * G - 1) / (64 * G);
     float4 va[ITER], vb[ITER];
     int goff[ITER];  // element offset of the node's first channel in the grid, -1: no such block / no such node
@@ -1987,17 +1878,15 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
         const int bn = (slot2 & 4) ? b47 : b03;
         if (bn >= 0) goff[it] = bn * (7 * NC) + cell;
 #pragma unroll
-        for (int gy = 0; gy < (G == 4 ? 2 : 1); ++gy)
-#pragma unroll
-          for (int gz = 0; gz < (G == 1 ? 1 : 2); ++gz) {
-            const int ly = y - 4 * gy, lz = z - 4 * gz;
-            if ((unsigned)ly < 6u && (unsigned)lz < 6u) {
-              const float4 *a = reinterpret_cast<const float4 *>(lds + (gy * 2 + gz) * WBUF) + AP::at(x, ly, lz);
-              const float4 pa = a[0], pb = a[AP::PLANE];
-              va[it] = make_float4(va[it].x + pa.x, va[it].y + pa.y, va[it].z + pa.z, va[it].w + pa.w);
-              vb[it] = make_float4(vb[it].x + pb.x, vb[it].y + pb.y, vb[it].z + pb.z, 0.f);
-            }
+        for (int gz = 0; gz < G; ++gz) {
+          const int lz = z - 4 * gz;
+          if ((unsigned)y < 6u && (unsigned)lz < 6u) {
+            const float4 *a = reinterpret_cast<const float4 *>(lds + gz * WBUF) + AP::at(x, y, lz);
+            const float4 pa = a[0], pb = a[AP::PLANE];
+            va[it] = make_float4(va[it].x + pa.x, va[it].y + pa.y, va[it].z + pa.z, va[it].w + pa.w);
+            vb[it] = make_float4(vb[it].x + pb.x, vb[it].y + pb.y, vb[it].z + pb.z, 0.f);
           }
+        }
       }
     }
 #pragma unroll
@@ -2010,26 +1899,6 @@ static __global__ __launch_bounds__(64 * G, 2) void p2g_tile_kernel(MpmDev mp, P
           if (val[ch] != 0.f) unsafeAtomicAdd(g + ch * NC, val[ch]);
       }
   }
-#ifdef ZS_P2GT_ENDWAIT
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#ifdef ZS_PROBE_P2G
-  {
-    const unsigned long long tp5 = P2G_NOW();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long tp6 = P2G_NOW();
-    P2G_STAMP(0, tp6 - tp0);
-    P2G_STAMP(1, tp1 - tp0);
-    P2G_STAMP(2, tp2 - tp1);
-    P2G_STAMP(3, tpWait);
-    P2G_STAMP(4, tp3 - tp2);
-    P2G_STAMP(5, tp4 - tp3);
-    P2G_STAMP(6, tp5 - tp4);
-    P2G_STAMP(7, tp6 - tp5);
-    P2G_STAMP(8, 1);
-    P2G_STAMP(9, tpRounds);
-  }
-#endif
 }
 
 // exact path for the queued particles (persistent grid-stride over a device-side count)
@@ -2082,7 +1951,7 @@ static __global__ __launch_bounds__(256) void grid_update_kernel(float *grid, si
 // constitutive update for the NEXT P2G, fused into the tail of G2P where the VALU is otherwise idle (G2P is HBM-bound, P2G
 // is VALU-bound by the SVD): stress(F_new, logJp) -> particles.stress (P F^T vol, unscaled), logJp updated.  Exactly what the
 // next P2G would compute from the same F (P2G.hpp:60-101); SMODEL < 0: disabled.
-template <int SMODEL, int LW = 0>
+template <int SMODEL, int LW = 0, bool NT = false>
 __device__ __forceinline__ void update_stress(const MpmDev &mp, const ParticlesDev &ps, POff<LW> o, float (&F)[9], const float (&C)[9]) {
   if constexpr (SMODEL >= 0) {
     float PF[9], Fl[9];
@@ -2091,14 +1960,14 @@ __device__ __forceinline__ void update_stress(const MpmDev &mp, const ParticlesD
     float lj = 0.f;
     if constexpr (model_uses_logjp(SMODEL)) lj = pload1<LW>(ps.logJp, o);
     model_stress<SMODEL>(mp.mat, lj, Fl, PF, C);
-    if constexpr (model_uses_logjp(SMODEL)) pstore1<LW>(ps.logJp, o, lj);
+    if constexpr (model_uses_logjp(SMODEL)) pstore1<LW, NT>(ps.logJp, o, lj);
     float S[STRESS_N];
     stress_pack(PF, S);
-    pstore<LW, STRESS_N>(ps.stress, o, S);
+    pstore<LW, STRESS_N, NT>(ps.stress, o, S);
   }
 }
 
-template <int SIDE, int SMODEL, int LW = 0>
+template <int SIDE, int SMODEL, int LW = 0, bool NT = false>
 __device__ __forceinline__ void g2p_finish_loaded(const MpmDev &mp, const ParticlesDev &ps, size_t i, float (&pos)[3], const float (&oldF)[9],
                                                   const float (&vel)[3], const float (&C)[9]) {
   const POff<LW> o = particle_offset<LW>(ps.pos.chns, i);
@@ -2106,11 +1975,11 @@ __device__ __forceinline__ void g2p_finish_loaded(const MpmDev &mp, const Partic
   for (int d = 0; d < 3; ++d) pos[d] += vel[d] * mp.dt;
   float F[9];
   advance_state<model_is_fluid(SMODEL)>(oldF, C, mp.dt, F);
-  pstore_state<LW, model_is_fluid(SMODEL)>(ps.F, o, F);
-  pstore<LW, 3>(ps.pos, o, pos);
-  pstore<LW, 3>(ps.vel, o, vel);
-  pstore<LW, 9>(ps.C, o, C);
-  update_stress<SMODEL, LW>(mp, ps, o, F, C);
+  pstore_state<LW, model_is_fluid(SMODEL), NT>(ps.F, o, F);
+  pstore<LW, 3, NT>(ps.pos, o, pos);
+  pstore<LW, 3, NT>(ps.vel, o, vel);
+  pstore<LW, 9, NT>(ps.C, o, C);
+  update_stress<SMODEL, LW, NT>(mp, ps, o, F, C);
 }
 template <int SIDE, int SMODEL>
 __device__ __forceinline__ void g2p_finish(const MpmDev &mp, const ParticlesDev &ps, size_t i, float (&pos)[3], const float (&vel)[3],
@@ -2180,11 +2049,13 @@ static __global__ __launch_bounds__(256) void g2p_global_kernel(MpmDev mp, Parti
   g2p_gather_global<SIDE, SMODEL>(mp, ps, i, t, grid, 4.f * dxi * dxi);
 }
 
-// v = sum W v_i and B = sum W v_i (xi - xp)^T over the 27 register-resident node velocities of the lane's cell, by sum
-// factorisation over z, then y, then x (W = wx wy wz): ~290 VALU ops instead of ~1000 for the node-by-node form of
-// G2P.hpp:54-66 (same sums, different association)
-__device__ __forceinline__ void g2p_gather_factorized(const MpmDev &mp, const Arena &ar, const float (&nv)[27][3], float D_inv,
-                                                      float (&vel)[3], float (&C)[9]) {
+// v = sum W v_i and B = sum W v_i (xi - xp)^T over the 27 node velocities of the particle's cell, read from an LDS arena (81
+// ds_read per particle), by sum factorisation over z, then y, then x (W = wx wy wz): ~290 VALU ops instead of ~1000 for the
+// node-by-node form of G2P.hpp:54-66 (same sums, different association).  The fused kernel is VALU-bound and needs the 81 VGPRs a
+// register-resident copy would cost for its P2G stencil.
+template <class AL>
+__device__ __forceinline__ void g2p_gather_lds(const MpmDev &mp, const Arena &ar, const float *a0, float D_inv, float (&vel)[3],
+                                               float (&C)[9]) {
   float xz[3], xy[3], xx[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -2192,23 +2063,35 @@ __device__ __forceinline__ void g2p_gather_factorized(const MpmDev &mp, const Ar
     xy[k] = ar.w[1][k] * node_off(mp.dx, k, ar.lp[1]);
     xz[k] = ar.w[2][k] * node_off(mp.dx, k, ar.lp[2]);
   }
-  float B[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // B[j][k]
+  float B[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
 #pragma unroll
   for (int j = 0; j < 3; ++j) vel[j] = 0.f;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     float t0[3] = {0.f, 0.f, 0.f}, t1[3] = {0.f, 0.f, 0.f}, t2[3] = {0.f, 0.f, 0.f};
+    // the slab's 27 node values first, then the arithmetic: one LDS latency per slab instead of one per pair of reads
+    float nv[3][3][3];
 #pragma unroll
     for (int bb = 0; bb < 3; ++bb) {
-      float s0[3], s1[3];
+      const float *g = a0 + AL::at(a, bb, 0);
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        const float v0 = nv[(a * 3 + bb) * 3 + 0][j], v1 = nv[(a * 3 + bb) * 3 + 1][j], v2 = nv[(a * 3 + bb) * 3 + 2][j];
-        s0[j] = fmaf(ar.w[2][2], v2, fmaf(ar.w[2][1], v1, ar.w[2][0] * v0));
-        s1[j] = fmaf(xz[2], v2, fmaf(xz[1], v1, xz[0] * v0));
-        t0[j] = fmaf(ar.w[1][bb], s0[j], t0[j]);
-        t1[j] = fmaf(xy[bb], s0[j], t1[j]);
-        t2[j] = fmaf(ar.w[1][bb], s1[j], t2[j]);
+        nv[bb][j][0] = g[j * AL::CH];
+        nv[bb][j][1] = g[j * AL::CH + 1];
+        nv[bb][j][2] = g[j * AL::CH + 2];
+      }
+    }
+    asm volatile("" ::: "memory");  // (keeps the compiler from sinking the reads back between the fmas)
+#pragma unroll
+    for (int bb = 0; bb < 3; ++bb) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const float v0 = nv[bb][j][0], v1 = nv[bb][j][1], v2 = nv[bb][j][2];
+        const float s0 = fmaf(ar.w[2][2], v2, fmaf(ar.w[2][1], v1, ar.w[2][0] * v0));
+        const float s1 = fmaf(xz[2], v2, fmaf(xz[1], v1, xz[0] * v0));
+        t0[j] = fmaf(ar.w[1][bb], s0, t0[j]);
+        t1[j] = fmaf(xy[bb], s0, t1[j]);
+        t2[j] = fmaf(ar.w[1][bb], s1, t2[j]);
       }
     }
 #pragma unroll
@@ -2220,91 +2103,12 @@ __device__ __forceinline__ void g2p_gather_factorized(const MpmDev &mp, const Ar
     }
   }
 #pragma unroll
-  for (int d = 0; d < 9; ++d) C[d] = B[d % 3][d / 3] * D_inv;  // C[d] += W v_i[d%3] xixp[d/3] D_inv (G2P.hpp:65)
+  for (int d = 0; d < 9; ++d) C[d] = B[d % 3][d / 3] * D_inv;
 }
 
-struct ArenaLds;
-template <class AL>
-__device__ __forceinline__ void g2p_gather_lds(const MpmDev &mp, const Arena &ar, const float *a0, float D_inv, float (&vel)[3],
-                                               float (&C)[9]);
-
-template <int SIDE, int SMODEL, int LW>
-static __global__ __launch_bounds__(64) void g2p_binned_kernel(MpmDev mp, ParticlesDev ps, BhtDev t, const float *grid, const int *binStart,
-                                                        const unsigned *cellCount, const int *nbr, int *stale, int *staleCount) {
-  using AL = ArenaLds;
-  constexpr int NC = SIDE * SIDE * SIDE;
-  __shared__ float arena[3 * AL::CH];
-  const int bin = (int)xcd_chunked(blockIdx.x, gridDim.x);
-  const int start = binStart[bin], end = binStart[bin + 1];
-  if (start == end) return;
-  const int lane = threadIdx.x;
-  const BinGeom<SIDE> geo(t, bin, mp.kscale);
-  for (int node = lane; node < 216; node += 64) {  // node decoded once for the 3 velocity channels
-    const int x = node / 36, y = (node / 6) % 6, z = node % 6;
-    int slot, cell;
-    arena_to_grid<SIDE>(geo.o, x, y, z, slot, cell);
-    const int bn = nbr[(size_t)geo.block * 8 + slot];
-    float *a = arena + AL::at(x, y, z);
-    const float *g = grid + ((size_t)(bn < 0 ? 0 : bn) * 7 + 1) * NC + cell;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) a[ch * AL::CH] = bn >= 0 ? g[ch * NC] : 0.f;
-  }
-  __syncthreads();
-  const int cx = lane >> 4, cy = (lane >> 2) & 3, cz = lane & 3;
-  // the 27 x 3 node velocities of this lane's cell, register resident for all its particles (re-reading them from LDS per
-  // particle frees 50 VGPRs but measured 8 % slower)
-  float nv[27][3];
-  {
-    const float *a0 = arena + AL::at(cx, cy, cz);
-#pragma unroll
-    for (int k = 0; k < 27; ++k) {
-      const float *g = a0 + AL::at(k / 9, (k / 3) % 3, k % 3);
-      nv[k][0] = g[0];
-      nv[k][1] = g[AL::CH];
-      nv[k][2] = g[2 * AL::CH];
-    }
-  }
-  const unsigned cnt = cellCount[(size_t)bin * 64 + lane];
-  const float dxi = mp.dxi;
-  const float D_inv = mp.D_inv;
-  RoundWalk walk(cnt, start);
-  int i0, i1;
-  bool any, any1;
-  bool has0 = walk.next(i0, any);
-  // x and the deformation state (F, or J for the fluid; the fluid's C is recomputed here, not read)
-  RecB<model_is_fluid(SMODEL) ? MPM_FLUID_NO_STRESS : ZS_MPM_FIXED_COROTATED, LW> cur, nxt;
-  if (has0) cur.load(ps, (size_t)i0);
-  while (any) {
-    const bool has1 = walk.next(i1, any1);
-    if (has1) nxt.load(ps, (size_t)i1);
-    if (has0) {
-      Arena ar;
-      make_arena(mp.dx, mp.dxi, cur.pos, ar);
-      const int ocx = ar.corner[0] - geo.org[0], ocy = ar.corner[1] - geo.org[1], ocz = ar.corner[2] - geo.org[2];
-      if (ocx == cx && ocy == cy && ocz == cz) {
-        float vel[3], C[9];
-        g2p_gather_factorized(mp, ar, nv, D_inv, vel, C);
-        g2p_finish_loaded<SIDE, SMODEL, LW>(mp, ps, (size_t)i0, cur.pos, cur.F, vel, C);
-      } else if ((unsigned)ocx < 4u && (unsigned)ocy < 4u && (unsigned)ocz < 4u) {
-        // another cell of the same bin (the particle moved since the last re-bin): its nodes are in the LDS arena
-        float vel[3], C[9];
-        g2p_gather_lds<AL>(mp, ar, arena + AL::at(ocx, ocy, ocz), D_inv, vel, C);
-        g2p_finish_loaded<SIDE, SMODEL, LW>(mp, ps, (size_t)i0, cur.pos, cur.F, vel, C);
-      } else {
-        stale[atomicAdd(staleCount, 1)] = i0;  // outside the bin: exact path (hash queries)
-      }
-    }
-    cur = nxt;
-    has0 = has1;
-    i0 = i1;
-    any = any1;
-  }
-}
-
-// ---- G2P with lane = PARTICLE (r06; the kernel zs_rocm_mpm_g2p launches for binned particles).  g2p_binned_kernel (kept for -DZS_G2P_AB
-// comparisons) maps lane = cell so that a lane keeps its cell's 27 x 3 node velocities in
-// registers -- and then runs the 860-instruction constitutive update at the lane occupancy of the rounds (~70 %: the fullest cell of a
-// bin sets the number of rounds).  Here a workgroup owns a grid block: its particles are ONE contiguous range of the compact order
+// ---- G2P with lane = PARTICLE (r06; the kernel zs_rocm_mpm_g2p launches for binned particles).  Its lane = cell predecessor kept a
+// cell's 27 x 3 node velocities in registers -- and then ran the 860-instruction constitutive update at the lane occupancy of the
+// rounds (~70 %: the fullest cell of a bin sets the number of rounds).  Here a workgroup owns a grid block: its particles are ONE contiguous range of the compact order
 // (bins of a block are consecutive), the waves take them 64 at a time (every lane busy, loads and stores fully coalesced), and a
 // particle gathers from the block's velocity arena in LDS at its own cell (sum-factorised, g2p_gather_lds).  A particle that moved to
 // another cell of the block since the last re-bin needs nothing special; one outside the block's cells takes the exact path.
@@ -2347,7 +2151,9 @@ static __global__ __launch_bounds__(SIDE == 8 ? 256 : 64) void g2p_packed_kernel
       if ((unsigned)ocx < (unsigned)SIDE && (unsigned)ocy < (unsigned)SIDE && (unsigned)ocz < (unsigned)SIDE) {
         float vel[3], C[9];
         g2p_gather_lds<AL>(mp, ar, arena + AL::at(ocx, ocy, ocz), D_inv, vel, C);
-        g2p_finish_loaded<SIDE, SMODEL, LW>(mp, ps, (size_t)i0, cur.pos, cur.F, vel, C);
+        // the particle state (124 B per particle, written once per step) by non-temporal stores: 3.43 -> 3.11 ms at 64 Mi particles;
+        // no effect on the fused kernels (measured)
+        g2p_finish_loaded<SIDE, SMODEL, LW, true>(mp, ps, (size_t)i0, cur.pos, cur.F, vel, C);
       } else {
         stale[atomicAdd(staleCount, 1)] = i0;  // the base node lies outside the block's cells: exact path (hash queries)
       }
@@ -2373,7 +2179,8 @@ static __global__ __launch_bounds__(256) void g2p_stale_kernel(MpmDev mp, Partic
 // P F^T vol never leave the chip (WRITE_ALL stores them for callers that want the full state).  Unfused, the same work
 // moves 296.5 B per particle and step.
 //
-// One workgroup of four waves owns a bin; lane = cell.  Per chunk of four rounds:
+// g2p2g_reorder_kernel, the kernel of the re-ordering step (the in-place step runs the role-split g2p2g_rs_kernel further down):
+// one workgroup of four waves owns a bin; lane = cell.  Per chunk of four rounds:
 //   phase 1   wave w runs round 4c + w through G2P (node velocities read from the LDS arena) + F update + constitutive model
 //             and stages {m, x', v', C', P F^T} of its 64 particles in LDS;
 //   phase 2   waves 0/1 accumulate mass + momentum (4 channels, 108 register accumulators) of staged rounds {0,1} / {2,3},
@@ -2386,63 +2193,6 @@ static __global__ __launch_bounds__(256) void g2p_stale_kernel(MpmDev mp, Partic
 // scatter afterwards).
 constexpr int G2P2G_NF = 25;
 constexpr int G2P2G_MQ_CAP = 512;  // in-bin movers a workgroup can take through its LDS queue (a bin holds ~512 particles)  // staged floats per particle: m, x(3), v(3), C(9), P F^T vol(9)
-
-// gather of g2p_gather_factorized with the node velocities read from the LDS arena (81 ds_read per particle; the fused
-// kernel is VALU-bound and needs the 81 VGPRs a register-resident copy would cost for its P2G stencil)
-template <class AL>
-__device__ __forceinline__ void g2p_gather_lds(const MpmDev &mp, const Arena &ar, const float *a0, float D_inv, float (&vel)[3],
-                                               float (&C)[9]) {
-  float xz[3], xy[3], xx[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    xx[k] = ar.w[0][k] * node_off(mp.dx, k, ar.lp[0]);
-    xy[k] = ar.w[1][k] * node_off(mp.dx, k, ar.lp[1]);
-    xz[k] = ar.w[2][k] * node_off(mp.dx, k, ar.lp[2]);
-  }
-  float B[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-#pragma unroll
-  for (int j = 0; j < 3; ++j) vel[j] = 0.f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    float t0[3] = {0.f, 0.f, 0.f}, t1[3] = {0.f, 0.f, 0.f}, t2[3] = {0.f, 0.f, 0.f};
-    // the slab's 27 node values first, then the arithmetic: one LDS latency per slab instead of one per pair of reads
-    float nv[3][3][3];
-#pragma unroll
-    for (int bb = 0; bb < 3; ++bb) {
-      const float *g = a0 + AL::at(a, bb, 0);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        nv[bb][j][0] = g[j * AL::CH];
-        nv[bb][j][1] = g[j * AL::CH + 1];
-        nv[bb][j][2] = g[j * AL::CH + 2];
-      }
-    }
-#ifndef ZS_GATHER_NO_FENCE
-    asm volatile("" ::: "memory");  // (keeps the compiler from sinking the reads back between the fmas)
-#endif
-#pragma unroll
-    for (int bb = 0; bb < 3; ++bb) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const float v0 = nv[bb][j][0], v1 = nv[bb][j][1], v2 = nv[bb][j][2];
-        const float s0 = fmaf(ar.w[2][2], v2, fmaf(ar.w[2][1], v1, ar.w[2][0] * v0));
-        const float s1 = fmaf(xz[2], v2, fmaf(xz[1], v1, xz[0] * v0));
-        t0[j] = fmaf(ar.w[1][bb], s0, t0[j]);
-        t1[j] = fmaf(xy[bb], s0, t1[j]);
-        t2[j] = fmaf(ar.w[1][bb], s1, t2[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      vel[j] = fmaf(ar.w[0][a], t0[j], vel[j]);
-      B[j][0] = fmaf(xx[a], t0[j], B[j][0]);
-      B[j][1] = fmaf(ar.w[0][a], t1[j], B[j][1]);
-      B[j][2] = fmaf(ar.w[0][a], t2[j], B[j][2]);
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < 9; ++d) C[d] = B[d % 3][d / 3] * D_inv;
-}
 
 // phase-2 consumer of one staged record.  STRESS = false: mass + momentum (4 channels), true: rhs (3 channels)
 template <bool STRESS>
@@ -2517,7 +2267,7 @@ template <int LW, bool DP, bool FLUID = false> struct RecG {  // fused-step inpu
 
 // W = wave index: phase 1 handles round 4c + W; phase 2 role: waves 0/1 take mass + momentum of staged rounds {0,1} / {2,3},
 // waves 2/3 the stress channels of rounds {0,1} / {2,3}; waves 0,2 accumulate into arena 0, waves 1,3 into arena 1
-template <int SIDE, int SMODEL, int LW, bool WRITE_ALL, int W, bool REORDER>
+template <int SIDE, int SMODEL, int LW, int W>
 __device__ __forceinline__ void g2p2g_body(const MpmDev &mp, const ParticlesDev &ps, const BinGeom<SIDE> &geo, int start, unsigned cnt,
                                            int lane, const float *varena, float *parena, float *stage, unsigned long long *smask,
                                            int *staleG, int *staleGCount, int *staleP, int *stalePCount, int *mq, int *mqCount,
@@ -2558,14 +2308,14 @@ __device__ __forceinline__ void g2p2g_body(const MpmDev &mp, const ParticlesDev 
   bool has0, has1, any, any1;
   next_chunk(i0, has0, any);
   RecG<LW, DP, model_is_fluid(SMODEL)> cur, nxt;
-  // re-ordering step (order != nullptr): slot i of the (new) binned order holds the particle stored at order[i] of the input
-  // buffer; everything this kernel stores goes to slot i of the output buffer, so the physical re-bin costs no pass of its own
-  if (has0) cur.load(ps, REORDER ? (size_t)order[i0] : (size_t)i0, REORDER ? inDelta : 0ll);
+  // slot i of the (new) binned order holds the particle stored at order[i] of the input buffer; everything this kernel stores goes
+  // to slot i of the output buffer, so the physical re-bin costs no pass of its own
+  if (has0) cur.load(ps, (size_t)order[i0], inDelta);
   int par = 0;  // stage / mask buffer of this chunk (double buffered: ONE barrier per chunk)
   while (any) {
     float *myStage = stage + (size_t)(par * 4 + W) * (G2P2G_NF * 64);
     next_chunk(i1, has1, any1);
-    if (has1) nxt.load(ps, REORDER ? (size_t)order[i1] : (size_t)i1, REORDER ? inDelta : 0ll);  // in flight during this chunk
+    if (has1) nxt.load(ps, (size_t)order[i1], inDelta);  // in flight during this chunk
     // ---------------- phase 1: G2P + update of this wave's round
     bool valid = false;
     if (has0) {
@@ -2576,7 +2326,7 @@ __device__ __forceinline__ void g2p2g_body(const MpmDev &mp, const ParticlesDev 
       // the bin altogether takes the exact path (hash queries into grid A)
       const int ocx = ar.corner[0] - geo.org[0], ocy = ar.corner[1] - geo.org[1], ocz = ar.corner[2] - geo.org[2];
       if ((unsigned)ocx >= 4u || (unsigned)ocy >= 4u || (unsigned)ocz >= 4u) {
-        if constexpr (REORDER) {  // the exact path works on slot i0 of the output buffer: give it the inputs
+        {  // the exact path works on slot i0 of the output buffer: give it the inputs
           const POff<LW> oo = particle_offset<LW>(ps.pos.chns, (size_t)i0);
           pstore<LW, 3>(ps.pos, oo, cur.pos);
           pstore_state<LW, model_is_fluid(SMODEL)>(ps.F, oo, cur.F);
@@ -2597,7 +2347,7 @@ __device__ __forceinline__ void g2p2g_body(const MpmDev &mp, const ParticlesDev 
         advance_state<model_is_fluid(SMODEL)>(cur.F, C, mp.dt, F);
         pstore_state<LW, model_is_fluid(SMODEL)>(ps.F, o, F);
         pstore<LW, 3>(ps.pos, o, pos);
-        if constexpr (REORDER) pstore1<LW>(ps.mass, o, cur.m);  // the mass moves with the particle
+        pstore1<LW>(ps.mass, o, cur.m);  // the mass moves with the particle
         {  // F has been stored above: the plastic models may project this local copy
           float lj = 0.f;
           if constexpr (DP) lj = cur.logJp;
@@ -2609,7 +2359,7 @@ __device__ __forceinline__ void g2p2g_body(const MpmDev &mp, const ParticlesDev 
         const int ncx = (int)floorf(pos[0] * dxi - 0.5f) - geo.org[0], ncy = (int)floorf(pos[1] * dxi - 0.5f) - geo.org[1],
                   ncz = (int)floorf(pos[2] * dxi - 0.5f) - geo.org[2];
         const bool moved = ncx != cx || ncy != cy || ncz != cz;
-        if (WRITE_ALL || moved) {
+        if (moved) {
           pstore<LW, 3>(ps.vel, o, vel);
           pstore<LW, 9>(ps.C, o, C);
           {
@@ -2617,8 +2367,6 @@ __device__ __forceinline__ void g2p2g_body(const MpmDev &mp, const ParticlesDev 
             stress_pack(PF, S);
             pstore<LW, STRESS_N>(ps.stress, o, S);
           }
-        }
-        if (moved) {
           bool queued = false;
           if ((unsigned)ncx < 4u && (unsigned)ncy < 4u && (unsigned)ncz < 4u) {
             const int slot = atomicAdd(mqCount, 1);
@@ -2678,11 +2426,11 @@ __device__ __forceinline__ void g2p2g_body(const MpmDev &mp, const ParticlesDev 
   __syncthreads();  // the post-pass and the flush read both arenas
 }
 
-template <int SIDE, int SMODEL, int LW, bool WRITE_ALL, bool REORDER = false>
-static __global__ __launch_bounds__(256) void g2p2g_binned_kernel(MpmDev mp, ParticlesDev ps, BhtDev t, const float *gridA, float *gridB,
-                                                           const int *binStart, const unsigned *cellCount, const int *nbr, int *staleG,
-                                                           int *staleGCount, int *staleP, int *stalePCount, int binBase,
-                                                           const int *order, long long inDelta) {
+template <int SIDE, int SMODEL, int LW>
+static __global__ __launch_bounds__(256) void g2p2g_reorder_kernel(MpmDev mp, ParticlesDev ps, BhtDev t, const float *gridA, float *gridB,
+                                                            const int *binStart, const unsigned *cellCount, const int *nbr, int *staleG,
+                                                            int *staleGCount, int *staleP, int *stalePCount, int binBase,
+                                                            const int *order, long long inDelta) {
   using AL = ArenaLds;
   constexpr int NC = SIDE * SIDE * SIDE;
   __shared__ float varena[3 * AL::CH];
@@ -2692,7 +2440,7 @@ static __global__ __launch_bounds__(256) void g2p2g_binned_kernel(MpmDev mp, Par
   __shared__ int mq[G2P2G_MQ_CAP];
   __shared__ int mqCount;
   if (threadIdx.x == 0) mqCount = 0;
-  const int bin = (int)xcd_chunked(blockIdx.x, gridDim.x) + binBase;  // a launch covers a range of blocks (boundary blocks first, see zs_rocm_mpm_g2p2g_range)
+  const int bin = (int)blockIdx.x + binBase;  // a launch covers a range of blocks (boundary blocks first, see zs_rocm_mpm_g2p2g_range)
   const int start = binStart[bin], end = binStart[bin + 1];
   if (start == end) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -2710,10 +2458,10 @@ static __global__ __launch_bounds__(256) void g2p2g_binned_kernel(MpmDev mp, Par
   for (int k = tid; k < 2 * 7 * AL::CH; k += 256) parena[k] = 0.f;
   const unsigned cnt = cellCount[(size_t)bin * 64 + lane];
   __syncthreads();
-  if (w == 0) g2p2g_body<SIDE, SMODEL, LW, WRITE_ALL, 0, REORDER>(mp, ps, geo, start, cnt, lane, varena, parena, stage, smask, staleG, staleGCount, staleP, stalePCount, mq, &mqCount, order, inDelta);
-  else if (w == 1) g2p2g_body<SIDE, SMODEL, LW, WRITE_ALL, 1, REORDER>(mp, ps, geo, start, cnt, lane, varena, parena, stage, smask, staleG, staleGCount, staleP, stalePCount, mq, &mqCount, order, inDelta);
-  else if (w == 2) g2p2g_body<SIDE, SMODEL, LW, WRITE_ALL, 2, REORDER>(mp, ps, geo, start, cnt, lane, varena, parena, stage, smask, staleG, staleGCount, staleP, stalePCount, mq, &mqCount, order, inDelta);
-  else g2p2g_body<SIDE, SMODEL, LW, WRITE_ALL, 3, REORDER>(mp, ps, geo, start, cnt, lane, varena, parena, stage, smask, staleG, staleGCount, staleP, stalePCount, mq, &mqCount, order, inDelta);
+  if (w == 0) g2p2g_body<SIDE, SMODEL, LW, 0>(mp, ps, geo, start, cnt, lane, varena, parena, stage, smask, staleG, staleGCount, staleP, stalePCount, mq, &mqCount, order, inDelta);
+  else if (w == 1) g2p2g_body<SIDE, SMODEL, LW, 1>(mp, ps, geo, start, cnt, lane, varena, parena, stage, smask, staleG, staleGCount, staleP, stalePCount, mq, &mqCount, order, inDelta);
+  else if (w == 2) g2p2g_body<SIDE, SMODEL, LW, 2>(mp, ps, geo, start, cnt, lane, varena, parena, stage, smask, staleG, staleGCount, staleP, stalePCount, mq, &mqCount, order, inDelta);
+  else g2p2g_body<SIDE, SMODEL, LW, 3>(mp, ps, geo, start, cnt, lane, varena, parena, stage, smask, staleG, staleGCount, staleP, stalePCount, mq, &mqCount, order, inDelta);
   // dense post-pass over the particles that changed cell inside this bin: one thread per particle, contributions added to the
   // bin's arena with LDS atomics (the register stencils of the lanes are keyed to cells).  Their state was stored by other
   // lanes of this workgroup a moment ago: read it at agent scope so that a stale L1 line (x was loaded in phase 1) cannot serve it.
@@ -2797,8 +2545,8 @@ static __global__ __launch_bounds__(256) void g2p2g_binned_kernel(MpmDev mp, Par
   }
 }
 // ---------------------------------------------------------------------------------------------------------------------------
-// Role-split variant of the fused pass (the default; g2p2g_binned_kernel above stays for the re-ordering step and for A/B runs
-// with ZS_ROCM_G2P2G_CLASSIC=1).  Measured on the four-wave kernel (tools/ablate.sh, 64 Mi particles): the costs of its parts
+// Role-split variant of the fused pass (the default; the four-wave g2p2g_reorder_kernel above stays for the re-ordering step).
+// Measured on the four-wave kernel (64 Mi particles): the costs of its parts
 // ADD UP instead of overlapping -- constitutive update 1.0 ms + phase-2 accumulation 0.9 + gather 0.5 + streaming skeleton 2.2
 // + head/tail of a bin 0.45 = 5.0 ms -- because at 223 VGPRs / 74.5 KB LDS only two waves share a SIMD, each of them parked 37 %
 // of its life (SQ_WAIT_ANY), and one wave alone issues a VALU instruction only every ~5 cycles.  The accumulators (27 nodes x 7
@@ -2810,12 +2558,6 @@ static __global__ __launch_bounds__(256) void g2p2g_binned_kernel(MpmDev mp, Par
 //                         arena belongs to one wave, so the final flush needs no barrier between its 27 phases
 // One barrier per chunk (stage double-buffered), 512 threads, 66 KB LDS: two workgroups = 16 waves per CU = 4 per SIMD.  The
 // per-record arena / weight set-up is repeated by four consumers instead of two (+190 VALU per 64 particles, +9 %).
-#ifdef ZS_PROBE  // measurement-only build (tools/ablate.sh PROBE): s_memtime stamps of a workgroup's phases, summed over all workgroups
-__device__ unsigned long long g_probe[16];
-#define ZS_STAMP(slot, t0) do { if ((threadIdx.x & 63) == 0 && (blockIdx.x & 127) == 0) atomicAdd(&g_probe[slot], (unsigned long long)(__builtin_readcyclecounter() - (t0))); } while (0)
-#else
-#define ZS_STAMP(slot, t0) do { } while (0)
-#endif
 template <int CS> struct ConsumerSet {  // CS 0: m + mv_x, 1: mv_y + mv_z, 2: f_x + f_y, 3: f_z
   static constexpr bool STRESS = CS >= 2;
   static constexpr bool MASS = CS == 0;
@@ -3002,14 +2744,7 @@ __device__ __forceinline__ void g2p2g_rs_producer(const MpmDev &mp, const Partic
       for (int ch = 0; ch < 3; ++ch) a[ch * AL::CH] = bn >= 0 ? g[ch * NC] : 0.f;
     }
   }
-#ifdef ZS_PROBE
-  const unsigned long long tP0 = __builtin_readcyclecounter();
-#endif
   __syncthreads();
-  ZS_STAMP(4, tP0);  // [4] producers: wait at the barrier behind the arena fill (grid loads landing)
-#ifdef ZS_PROBE
-  unsigned long long tBar = 0, tP1 = __builtin_readcyclecounter();
-#endif
   for (int it = 0; it <= nchunks; ++it) {
     if (it < nchunks) {
       const int par = it & 1;
@@ -3099,20 +2834,8 @@ __device__ __forceinline__ void g2p2g_rs_producer(const MpmDev &mp, const Partic
         if (lane == 0) smask[par * 4 + W] = vm;
       }
     }
-#ifdef ZS_PROBE
-    const unsigned long long tb = __builtin_readcyclecounter();
     __syncthreads();
-    tBar += __builtin_readcyclecounter() - tb;
-#else
-    __syncthreads();
-#endif
   }
-#ifdef ZS_PROBE
-  if (lane == 0 && (blockIdx.x & 127) == 0) {
-    atomicAdd(&g_probe[5], tBar);                                    // [5] producers: time inside the per-chunk barriers
-    atomicAdd(&g_probe[6], __builtin_readcyclecounter() - tP1);      // [6] producers: the chunk loop
-  }
-#endif
 }
 
 template <int SIDE, int SMODEL, int LW, bool WRITE_ALL>
@@ -3128,10 +2851,7 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_rs_kernel(MpmDev mp, Part
   __shared__ int mq[G2P2G_MQ_CAP];
   __shared__ int mqCount;
   if (threadIdx.x == 0) mqCount = 0;
-#ifdef ZS_PROBE
-  const unsigned long long tEntry = __builtin_readcyclecounter();
-#endif
-  const int bin = (int)xcd_chunked(blockIdx.x, gridDim.x) + binBase;
+  const int bin = (int)blockIdx.x + binBase;
   const int start = binStart[bin], end = binStart[bin + 1];
   if (start == end) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -3153,10 +2873,8 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_rs_kernel(MpmDev mp, Part
   else if (w == 5) g2p2g_rs_consumer<1>(mp, lane, nchunks, stage, smask, parena);
   else if (w == 6) g2p2g_rs_consumer<2>(mp, lane, nchunks, stage, smask, parena);
   else g2p2g_rs_consumer<3>(mp, lane, nchunks, stage, smask, parena);
-  ZS_STAMP(w < 4 ? 0 : 1, tEntry);  // [0] producers / [1] consumers: entry -> end of the role body (summed over 4 waves each)
   __syncthreads();  // all channel sets are in the arena
-  ZS_STAMP(2, tEntry);              // [2] entry -> past the barrier behind the bodies (8 waves)
-  // in-bin movers: dense post-pass with LDS atomics (see g2p2g_binned_kernel)
+  // in-bin movers: dense post-pass with LDS atomics (see g2p2g_reorder_kernel)
   {
     // The queued particles' state was stored by OTHER waves of this workgroup during the loop, with plain stores; the reads below are
     // agent-scope loads.  A barrier orders instructions, not the arrival of stores at L2 (outside threadgroup-split mode a workgroup-scope
@@ -3231,10 +2949,6 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_rs_kernel(MpmDev mp, Part
       staleGCount[9] = 1;  // mass for a node whose block is not in the partition
     }
   }
-  ZS_STAMP(3, tEntry);  // [3] entry -> exit (8 waves)
-#ifdef ZS_PROBE
-  if (threadIdx.x == 0 && (blockIdx.x & 127) == 0) atomicAdd(&g_probe[7], 1ull);  // sampled workgroups
-#endif
 }
 // queue G: gather from grid A with hash queries (stores the full state), then scatter to grid B; queue P: scatter only
 template <int SIDE, int SMODEL>

@@ -102,15 +102,9 @@ template <int SIDE> __device__ __forceinline__ int neighbour_bin(const int *nbr2
 //     round -- while its grid terms take the list as above; no record, no slot_rehome_kernel.  The claim words' high halves then count
 //     the arrivals from inside the block, written once per block after its last barrier.
 // Departures and ticket counts are folded into the occupancy words by slot_commit_kernel.
-#ifndef ZS_PROD_XLIST
-#define ZS_PROD_XLIST 1  // the list of the last chunk is scattered by the (then idle) producer waves
-#endif
 constexpr int SL_NG = 9;       // staged entry groups of 64: a chunk being produced (4) + the chunk being consumed (4) + a straddling round
 constexpr int SL_KMAX = 32;    // rounds per bin the 32-bit occupancy words allow
-#ifndef ZS_SL_ARRQ
-#define ZS_SL_ARRQ 4
-#endif
-constexpr int SL_ARRQ = ZS_SL_ARRQ;     // in-bin arrivals one cell takes per chunk through the consumers' queue
+constexpr int SL_ARRQ = 4;     // in-bin arrivals one cell takes per chunk through the consumers' queue
 constexpr int SL_XQ = 64;      // movers per chunk whose grid contributions the consumers add with global atomics (new cell in another bin, or
                                // arrival queue full); more: scattered from their outbox records after the loop
 
@@ -603,7 +597,7 @@ __device__ __forceinline__ void g2p2g_slot_producer(const MpmDev &mp, const Part
   }
   {  // nothing left to produce (the consumers accumulate the rounds of the last chunk): the last chunk's global-atomic list
     SLP_T0(tB);
-    if (ZS_PROD_XLIST && nchunks > 0) {
+    if (nchunks > 0) {  // the list of the last chunk is scattered by the (then idle) producer waves
       const int par = (nchunks - 1) % 3;
       const int nx = xCnt[par] < (unsigned)SL_XQ ? (int)xCnt[par] : SL_XQ;
       slot_xlist_scatter<SIDE, W>(mp, geo, stage, xq[par], nx, lane, sh.nbrBlk, A);
@@ -688,7 +682,7 @@ __device__ __forceinline__ void g2p2g_slot_consumer(const MpmDev &mp, const BinG
       // list of the LAST chunk is taken by the producer waves, which have nothing left to produce in that iteration
       const int nx = xCnt[par] < (unsigned)SL_XQ ? (int)xCnt[par] : SL_XQ;
       if (CS == 0 && lane == 0) xCnt[(it + 1) % 3] = 0u;
-      if (!ZS_PROD_XLIST || it < nchunks) slot_xlist_scatter<SIDE, CS>(mp, geo, stage, xq[par], nx, lane, nbrBlk, A);
+      if (it < nchunks) slot_xlist_scatter<SIDE, CS>(mp, geo, stage, xq[par], nx, lane, nbrBlk, A);
       if (CS == 0) {
         SLP_ADD(14, tX);  // [14] consumer: global-atomic list
         SLP_PUT(12, nx);  // [12] entries of the list

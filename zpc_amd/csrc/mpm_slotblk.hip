@@ -496,7 +496,7 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   const BlkShared sh{s_varena, s_parena, s_stage, s_smask, s_tab, s_masks, s_clr, s_arrLocal, s_arrCnt, s_arrQ, s_xCnt, s_xq, s_nbrBlk, s_nbrBin, s_nbr8,
                      s_cnt, s_total, s_gbase, s_nch, s_binQ, s_oc, s_chBin, s_chIdx, s_desc, &s_done, s_sums};
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int blk = (int)xcd_chunked(blockIdx.x, gridDim.x) + A.binBase / 8;
+  const int blk = (int)blockIdx.x + A.binBase / 8;
   const int bin0 = blk * 8;
   SLP_T0(tStart);
   // occupancy of the block's 8 bins: wave w <-> bin w

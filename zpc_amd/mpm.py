@@ -134,16 +134,15 @@ class MpmTransfer:
 
         order = how the blocks are numbered (the reference leaves it to the race of the inserting threads):
           "insertion"         the table's own dense indices (the race)
-          None / "holders_lex" the blocks that hold particles in lexicographic key order, the apron blocks behind them (in the order
-                              of their race: they hold no particle, the per-block kernels leave them at once)
+          None / "holders_lex" the blocks that hold particles in lexicographic key order, the apron blocks behind them (also in key
+                              order: they hold no particle, the per-block kernels leave them at once)
           "lex"               every block in lexicographic key order
           "morton"            every block along the Z-order curve
         axes (holders_lex / lex): the key components from most to least significant, default (0, 1, 2); the last one changes fastest
         along the numbering.  The fused block kernel runs 1.3 % faster with the cloud's longest axis last (bench.py passes that).
         The numbering changes no result beyond the order of the atomic sums, only which workgroups run side by side
         (profiles/r06_p2g.md, section 4b)."""
-        import os
-        order = os.environ.get("ZS_ROCM_CANONICAL_PARTITION") or order or "holders_lex"   # (the variable: tools/r06_order.sh's A/B)
+        order = order or "holders_lex"
         if order not in ("insertion", "holders_lex", "lex", "morton"):
             raise ValueError(f"build_partition: unknown block order {order!r}")
         self.table = Bht(3, int(expected_blocks))
@@ -156,15 +155,13 @@ class MpmTransfer:
             self.table.canonicalize(self.pol, axes)
             self.pol.syncCtx()
             n_holders = self.table.size()
-        if os.environ.get("ZS_ROCM_HOLDER_ORDER"):   # measurement only (tools/r06_order2.sh)
-            self._measurement_holder_order(os.environ["ZS_ROCM_HOLDER_ORDER"])
         m = int(margin)
         self.partition_margin = m   # (repartition_slotted() keeps the same travel room unless told otherwise)
         lo, hi = (C.c_int * 3)(-m, -m, -m), (C.c_int * 3)(2 + m, 2 + m, 2 + m)
         L.zs_rocm_mpm_enlarge_sparsity(self.pol.handle, self.table.handle, lo, hi, self.kstride)
         self.pol.syncCtx()
-        if order == "holders_lex" and not os.environ.get("ZS_ROCM_APRON_RACE"):   # the apron blocks in key order too: the whole numbering is reproducible
-            self.table.canonicalize(self.pol, axes, first=n_holders)                    # (the variable: A/B of profiles/r06_p2g.md, section 4b)
+        if order == "holders_lex":   # the apron blocks in key order too: the whole numbering is reproducible
+            self.table.canonicalize(self.pol, axes, first=n_holders)
             self.pol.syncCtx()
         if order == "morton":
             self.table.order_morton(self.pol)
@@ -181,49 +178,6 @@ class MpmTransfer:
         L.zs_rocm_mpm_build_neighbors(self.pol.handle, self.table.handle, self.nbr.data_ptr(), self.kstride)
         self.binned = False
         return self.nblocks
-
-    def _measurement_holder_order(self, xp):
-        """MEASUREMENT ONLY (profiles/r06_block_order_*.txt): renumber the blocks that hold particles (the table right after ComputeSparsity).
-        "120" = key axis 1 most significant, then 2, then 0; "120:2,4,4" = the same inside and across tiles of 2 x 4 x 4 blocks; "m" = Z-order
-        curve; suffix "s17": position p holds the (17 p mod n)-th holder of that order; suffix "x": XCD k (workgroup number mod 8) walks the
-        k-th contiguous eighth."""
-        import ctypes
-        self.pol.syncCtx()
-        n0 = self.table.size()
-        v = self.table.view()
-        k = torch.empty(n0 * 3, dtype=torch.int32, device=self.device)
-        ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.activeKeys), ctypes.c_size_t(n0 * 12), 3)
-        k = k.view(n0, 3).to(torch.int64) // self.kstride
-        k = k - k.min(dim=0).values
-        if xp == "m":
-            code = torch.zeros(n0, dtype=torch.int64, device=self.device)
-            for bit in range(16):
-                for d in range(3):
-                    code |= ((k[:, d] >> bit) & 1) << (3 * bit + (2 - d))
-        else:
-            ax = [int(c) for c in xp[:3]]
-            t = [int(c) for c in xp.rstrip("x").split("s")[0].split(":")[1].split(",")] if ":" in xp else [1, 1, 1]
-            code = torch.zeros(n0, dtype=torch.int64, device=self.device)
-            for d in ax:
-                code = code * 4096 + k[:, d] // t[d]
-            for d in ax:
-                code = code * t[d] + k[:, d] % t[d]
-        perm = torch.argsort(code).to(torch.int32).contiguous()
-        if "s" in xp:   # "021s17": position p holds the (17 p mod n)-th holder of the sorted order (n made coprime by dropping a tail)
-            st = int(xp.split("s")[1])
-            import math
-            nn = n0
-            while math.gcd(nn, st) != 1:
-                nn -= 1
-            pos = (torch.arange(nn, device=self.device, dtype=torch.int64) * st) % nn
-            perm = torch.cat([perm[pos], perm[nn:]]).contiguous()
-        if xp.endswith("x"):   # XCD k (workgroup number mod 8) walks the k-th contiguous eighth of the sorted holders
-            q = n0 // 8
-            pos = torch.arange(8 * q, device=self.device)
-            perm = torch.cat([perm[(pos % 8) * q + pos // 8], perm[8 * q:]]).contiguous()
-        torch.cuda.synchronize()
-        self.table.reorder(self.pol, perm.data_ptr(), scatter=False)
-        self.pol.syncCtx()
 
     def adopt_partition(self, active_keys_ptr, nblocks):
         """Use a partition numbered elsewhere -- the `_activeKeys` of a zs::HashTable<i32,3,int> built by
