@@ -421,6 +421,24 @@ def _id_box_step(pol, oracle, model, grid_n, cells, drift, box_lo, steps_before,
     diff = np.abs(gridB - om.grid)
     out["grid"] = [float(diff[:, ch, :][interior].max() / scale[ch]) for ch in range(7)]
     out["grid_mass_interior"] = float(om.grid[:, 0, :][interior].min())
+    # in addition: every identified particle and every interior node within its own float64 bound (tests/ref64.py), from the GPU's
+    # own inputs (the node velocities before the step, the state the step stored)
+    import ref64
+    kscale = side // mt.kstride
+    wa = ref64.world_nodes(kk, gridA, side, kscale)
+    r = ref64.g2p64((wa[0], wa[1][:, 1:4]), a[:, 1:4], dx, dt, F=a[:, 16:25] if model == 0 else None)
+    out["ref64_particles"] = [ref64.check_particles(b[:, 1:4], r["x"], r["b_x"], "sub-box x"),
+                              ref64.check_particles(b[:, 4:7], r["v"], r["b_v"], "sub-box v"),
+                              ref64.check_particles(b[:, 7:16], r["C"], r["b_C"], "sub-box C")]
+    if model == 0:
+        out["ref64_particles"].append(ref64.check_particles(b[:, 16:25], r["F"], r["b_F"], "sub-box F"))
+    del r
+    ref = ref64.p2g64(b[:, 0], b[:, 1:4], b[:, 4:7], b[:, 7:16], dx, dt)
+    wb = ref64.world_nodes(kk, gridB, side, kscale)
+    inner = interior.ravel()
+    rows = ref.lookup(wb[0][inner])
+    assert (rows >= 0).all()
+    out["ref64_grid"] = ref64.check_grid(ref.subset(rows), (wb[0][inner], wb[1][inner]), range(4), "sub-box interior nodes")[:4].tolist()
     return out
 
 
@@ -433,6 +451,8 @@ def test_config4_sand_64m_slotted_moving_subbox_vs_oracle(pol, oracle):
     assert r["movers_in_step"] > 1_000_000 and r["changed_cell_in_step"] > 1000, r   # the step under test moves particles between cells
     assert r["x"] <= 1e-6 and r["v"] <= 2e-4 and r["C"] <= 2e-4 and r["F"] <= 2e-5 and r["logJp"] <= 2e-5, r
     assert max(r["grid"]) <= 2e-4 and r["grid_mass_interior"] > 0, r
+    assert max(r["ref64_grid"]) <= 1 and max(r["ref64_particles"]) <= 1, r   # (ref64's checks raise on their own; recorded in r)
+    print("REF64 sub-box grid %s particles %s" % (r["ref64_grid"], r["ref64_particles"]))
 
 
 def test_config3_jello_8m_slotted_moving_subbox_vs_oracle(pol, oracle):
@@ -441,6 +461,8 @@ def test_config3_jello_8m_slotted_moving_subbox_vs_oracle(pol, oracle):
     r = _id_box_step(pol, oracle, 0, 256, (100, 100, 100), (0.0, -0.5, 0.0), (112, 32, 112), steps_before=8)
     assert r["x"] <= 1e-6 and r["v"] <= 2e-4 and r["C"] <= 2e-4 and r["F"] <= 2e-5, r
     assert max(r["grid"]) <= 2e-4 and r["grid_mass_interior"] > 0, r
+    assert max(r["ref64_grid"]) <= 1 and max(r["ref64_particles"]) <= 1, r   # (ref64's checks raise on their own; recorded in r)
+    print("REF64 sub-box grid %s particles %s" % (r["ref64_grid"], r["ref64_particles"]))
 
 
 # ------------------------------------------------------------------------------------------------ r04: conservation across re-partitions

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from util import rng, make_cloud, OracleMpm, ptr, YIELD_SURFACE
+from util import rng, make_cloud, make_uneven_cloud, move_after_binning, OracleMpm, ptr, YIELD_SURFACE
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -271,25 +271,9 @@ def test_cached_stress_p2g_kernel_variants_vs_oracle(pol, oracle, variant, side)
     mt.rebin()
     mt.update_stress()
     # move a sixth of the cloud's inner particles by up to 1.2 cells AFTER binning (two cells from its faces: they stay inside the partition)
-    r = rng(59)
-    lo, hi = pos.min(0) + 2 * dx, pos.max(0) - 2 * dx
-    moved = (r.random(n) < 0.17) & ((pos >= lo) & (pos <= hi)).all(1)
+    pos2, moved = move_after_binning(mt, pos)
     assert moved.sum() > 100
-    pos2 = pos.copy()
-    pos2[moved] += (r.random((moved.sum(), 3)).astype(np.float32) - 0.5) * 2.4 * dx
-    order = mt.order.cpu().numpy()
-    d = mt.download()
-    d["x"] = pos2[order]
-    a = np.concatenate([d["m"][:, None], d["x"], d["v"], d["C"], d["F"]], axis=1)
-    cols = torch.zeros(n, mt.nchn, dtype=torch.float32, device="cuda")
-    cols[:, :a.shape[1]] = torch.from_numpy(a).cuda()
-    stress = torch.empty(n, mt.nchn, dtype=torch.float32, device="cuda")
     lib = __import__("zpc_amd").lib()
-    lib.zs_rocm_tv_to_aos_f32(pol.handle, mt.buf.data_ptr(), n, mt.nchn, mt.L, stress.data_ptr())
-    pol.syncCtx()
-    cols[:, mt.off["PF"]:mt.off["PF"] + 6] = stress[:, mt.off["PF"]:mt.off["PF"] + 6]
-    lib.zs_rocm_tv_from_aos_f32(pol.handle, cols.data_ptr(), n, mt.nchn, mt.L, mt.buf.data_ptr())
-    pol.syncCtx()
     parts = mt.particles()
     if variant == "tile_separate_bases":
         other = mt.buf.clone()   # same layout, another allocation: the mass port no longer sits 64 floats in front of x
@@ -785,19 +769,11 @@ def test_slotted_uneven_cells_many_sparse_rounds_vs_oracle(pol, oracle, side):
     (entry table, staged-entry ring, rounds completing in the middle of a chunk).  Four slotted steps with motion against the oracle."""
     from zpc_amd.mpm import MpmTransfer
     dx, dt = 1.0 / 64, 1e-3
-    g = rng(2024 + side)
     # a 10^3-cell box; per cell a particle count drawn from a heavy-tailed distribution
-    cells = np.stack(np.meshgrid(np.arange(10), np.arange(10), np.arange(10), indexing="ij"), -1).reshape(-1, 3)
     # (a cell needs free rounds for a step's arrivals on top of the particles it holds: K = 32 rounds, up to 22 particles at the start)
-    cnt = np.minimum(1 + (g.pareto(1.2, cells.shape[0]) * 2).astype(int), 22)
-    org = np.array([0.30, 0.31, 0.29])
-    pos = np.concatenate([org + (c + 0.5 + g.random((k, 3))) * dx for c, k in zip(cells, cnt)]).astype(np.float32)  # base node = c
+    mass, pos, vel, Cm, F, cnt = make_uneven_cloud(2024 + side)   # ~0.2-0.25 cell per step
     n = pos.shape[0]
     assert cnt.max() >= 20 and (cnt == 1).sum() > 50
-    mass = (1000.0 * dx ** 3 / 8 * (1 + 1e-3 * np.arange(n) / n)).astype(np.float32)
-    vel = (0.3 * g.standard_normal((n, 3)) + np.array([3.0, -4.0, 2.0])).astype(np.float32)  # ~0.2-0.25 cell per step
-    Cm = (0.1 * g.standard_normal((n, 9))).astype(np.float32)
-    F = (np.eye(3).reshape(1, 9) + 0.01 * g.standard_normal((n, 9))).astype(np.float32)
     lj = np.zeros(n, np.float32)
     vol = dx ** 3 / 8
     om = OracleMpm(oracle, 1, dx, dt, side, vol)

@@ -4,7 +4,7 @@ slot_rehome_kernel (zpc_amd/csrc/mpm_slot.hpp, slot_produce_entry; mpm_slotblk.h
 import numpy as np
 import pytest
 
-from util import rng, make_cloud, OracleMpm
+from util import rng, make_drifting_cloud, make_full_cell_cloud, OracleMpm
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -49,11 +49,8 @@ def test_slotted_block_movers_across_bin_and_block_faces_vs_oracle(pol, oracle):
     here from the positions before and after the step.  After the last step every particle agrees with the oracle."""
     from zpc_amd.mpm import MpmTransfer
     dx, dt, side, model = 1.0 / 64, 1e-3, 8, 1
-    mass, pos, vel, Cm, F = make_cloud(8, dx, 2, seed=4242, vel_scale=0.1)
+    mass, pos, vel, Cm, F = make_drifting_cloud()                      # identity-tagged, ~0.1 cell per step
     n = pos.shape[0]
-    mass = (mass * (1 + 1e-3 * np.arange(n) / n)).astype(np.float32)   # identity tag
-    assert len(np.unique(mass)) == n
-    vel += np.array([1.6, -1.5, 1.4], np.float32)                      # ~0.1 cell per step
     vol = dx ** 3 / 8
     lj = (0.01 * rng(7).standard_normal(n)).astype(np.float32)
     om = OracleMpm(oracle, model, dx, dt, side, vol)
@@ -116,17 +113,8 @@ def test_slotted_full_destination_cell_in_another_bin_of_the_block_keeps_the_mov
     sent == re-homed, and every particle is still stored."""
     from zpc_amd.mpm import MpmTransfer
     dx, dt, side, K = 1.0 / 64, 1e-3, 8, 8
-    g = rng(99)
-    yz = 35.0 + 0.3 * (g.random((K + 4, 2)) - 0.5)
-    xa = np.full(4, 36.49)                     # cell 35 (X in [35.5, 36.5)), about to cross into cell 36
-    xb = 37.0 + 0.2 * (g.random(K) - 0.5)      # cell 36, centred
-    pos = (np.concatenate([np.stack([xa, yz[:4, 0], yz[:4, 1]], 1), np.stack([xb, yz[4:, 0], yz[4:, 1]], 1)]) * dx).astype(np.float32)
+    mass, pos, vel, Cm, F = make_full_cell_cloud(dx, K)
     n = pos.shape[0]
-    mass = (1000.0 * dx ** 3 / 8 * (1 + 1e-3 * np.arange(n) / n)).astype(np.float32)
-    vel = np.zeros((n, 3), np.float32)
-    vel[:4, 0] = 2.0
-    Cm = np.zeros((n, 9), np.float32)
-    F = np.tile(np.eye(3, dtype=np.float32).reshape(1, 9), (n, 1))
     mt = MpmTransfer(pol, n, dx, dt, model=0, side=side, volume=dx ** 3 / 8, cache_stress=True)
     mt.upload(mass, pos, vel, Cm, F, None)
     mt.build_partition(n, margin=1)

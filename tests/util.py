@@ -65,6 +65,157 @@ def make_cloud(n_side, dx, ppc_side=2, origin=(0.30, 0.31, 0.29), seed=3, noise=
     return mass, pos, vel, Cm, F
 
 
+def tag_masses(mass):
+    """pairwise different masses (identity tag: particles are matched by mass after the slotted / re-ordering steps)"""
+    n = len(mass)
+    out = (mass * (1 + 1e-3 * np.arange(n) / n)).astype(np.float32)
+    assert len(np.unique(out)) == n
+    return out
+
+
+def make_drifting_cloud(seed=4242, drift=(1.6, -1.5, 1.4), vel_scale=0.1):
+    """identity-tagged 8^3-cell cloud drifting ~0.1 cell per step (dt = 1e-3) on all three axes: its particles cross bin and block faces"""
+    dx = 1.0 / 64
+    mass, pos, vel, Cm, F = make_cloud(8, dx, 2, seed=seed, vel_scale=vel_scale)
+    vel += np.array(drift, np.float32)
+    return tag_masses(mass), pos, vel, Cm, F
+
+
+def make_uneven_cloud(seed, ncell=10, cap=22):
+    """ncell^3-cell box whose per-cell particle count is heavy-tailed (up to `cap` in a cell beside cells with one), drifting ~0.2 cell
+    per step (dt = 1e-3); identity-tagged masses"""
+    dx = 1.0 / 64
+    g = rng(seed)
+    cells = np.stack(np.meshgrid(np.arange(ncell), np.arange(ncell), np.arange(ncell), indexing="ij"), -1).reshape(-1, 3)
+    cnt = np.minimum(1 + (g.pareto(1.2, cells.shape[0]) * 2).astype(int), cap)
+    org = np.array([0.30, 0.31, 0.29])
+    pos = np.concatenate([org + (c + 0.5 + g.random((k, 3))) * dx for c, k in zip(cells, cnt)]).astype(np.float32)  # base node = c
+    n = pos.shape[0]
+    mass = (1000.0 * dx ** 3 / 8 * (1 + 1e-3 * np.arange(n) / n)).astype(np.float32)
+    vel = (0.3 * g.standard_normal((n, 3)) + np.array([3.0, -4.0, 2.0])).astype(np.float32)
+    Cm = (0.1 * g.standard_normal((n, 9))).astype(np.float32)
+    F = (np.eye(3).reshape(1, 9) + 0.01 * g.standard_normal((n, 9))).astype(np.float32)
+    return mass, pos, vel, Cm, F, cnt
+
+
+def make_mixed_cloud(n_side, dx, origin=(0.30, 0.31, 0.29), seed=5, vel_scale=0.5):
+    """make_cloud with three abutting slabs along x of per-particle mass m, 1e-3 m and 1e-6 m, and neighbouring particles moving in
+    opposite directions (the lattice parity flips the sign of v and C), so that momentum cancels at the nodes; free surface on every side"""
+    ppc = 2
+    mass, pos, vel, Cm, F = make_cloud(n_side, dx, ppc, origin=origin, seed=seed, vel_scale=vel_scale)
+    k = n_side * ppc
+    idx = np.stack(np.meshgrid(np.arange(k), np.arange(k), np.arange(k), indexing="ij"), -1).reshape(-1, 3)
+    slab = np.minimum(3 * idx[:, 0] // k, 2)
+    mass = (mass * np.array([1.0, 1e-3, 1e-6], np.float32)[slab]).astype(np.float32)
+    sign = np.where(idx.sum(1) % 2 == 0, 1.0, -1.0).astype(np.float32)[:, None]
+    base = np.array([0.8, -0.6, 0.7], np.float32)
+    vel = (sign * base + 0.05 * vel).astype(np.float32)
+    Cm = (sign * np.abs(Cm)).astype(np.float32)
+    return mass, pos, vel, Cm, F
+
+
+def make_edge_cloud(dx=1.0 / 64, seed=17, vel_scale=0.2, drift=(0.0, 0.0, 0.0)):
+    """8^3-cell cloud straddling world coordinate 0 whose particles sit on the arena's edges, one axis each: X - 0.5 integral (one
+    weight is 0), X = 0.5 - 2^-25 and 0.5 - 2^-24 (lpn rounds up to 1.5), X = -0.5 - 2^-24 (X - 0.5 rounds to an integer: lpn just below
+    0.5), and the first / last 1e-3 cell of base cells on bin faces (cell = 0, 3 mod 4) and block faces (0, 7 mod 8), at negative
+    coordinates too.  dx must be a power of two (the edge positions are then exact)."""
+    mass, pos, vel, Cm, F = make_cloud(8, dx, 2, origin=(-4 * dx, -4 * dx, -4 * dx), seed=seed, vel_scale=vel_scale)
+    n = pos.shape[0]
+    vel += np.array(drift, np.float32)
+    X = [np.float32(c + 0.5) for c in range(-4, 4)]
+    X += [np.float32(0.5) - np.float32(2.0 ** -25), np.float32(0.5) - np.float32(2.0 ** -24), np.float32(-0.5) - np.float32(2.0 ** -24)] * 3
+    X += [np.float32(c + 0.5 + e) for c in (-5, -4, -1, 0, 3) for e in (1e-3, 1 - 1e-3)]
+    g = rng(seed + 1)
+    picked = g.choice(n, 3 * len(X), replace=False)
+    for j, i in enumerate(picked):
+        pos[i, j % 3] = X[j % len(X)] * np.float32(dx)
+    return mass, pos, vel, Cm, F
+
+
+def make_full_cell_cloud(dx, K, seed=99):
+    """four particles just below the +x face of cell 35 moving (v_x = 2) into cell 36, which holds K particles at rest (the full
+    destination cell of the slotted step); identity-tagged masses, C = 0, F = I"""
+    g = rng(seed)
+    yz = 35.0 + 0.3 * (g.random((K + 4, 2)) - 0.5)
+    xa = np.full(4, 36.49)                     # cell 35 (X in [35.5, 36.5)), about to cross into cell 36
+    xb = 37.0 + 0.2 * (g.random(K) - 0.5)      # cell 36, centred
+    pos = (np.concatenate([np.stack([xa, yz[:4, 0], yz[:4, 1]], 1), np.stack([xb, yz[4:, 0], yz[4:, 1]], 1)]) * dx).astype(np.float32)
+    n = pos.shape[0]
+    mass = (1000.0 * dx ** 3 / 8 * (1 + 1e-3 * np.arange(n) / n)).astype(np.float32)
+    vel = np.zeros((n, 3), np.float32)
+    vel[:4, 0] = 2.0
+    Cm = np.zeros((n, 9), np.float32)
+    F = np.tile(np.eye(3, dtype=np.float32).reshape(1, 9), (n, 1))
+    return mass, pos, vel, Cm, F
+
+
+def move_after_binning(mt, pos, seed=59, frac=0.17, reach=2.4):
+    """move a fraction of the inner particles of a binned MpmTransfer (two cells from the cloud's faces: they stay inside the
+    partition) by up to reach / 2 cells on every axis AFTER binning: in-bin movers and out-of-bin movers for the P2G kernels.
+    Every other channel of the particle buffer is kept.  Returns (new positions in the original numbering, moved mask)."""
+    import torch
+    from zpc_amd import lib
+    dx = mt.params.dx
+    n = pos.shape[0]
+    r = rng(seed)
+    lo, hi = pos.min(0) + 2 * dx, pos.max(0) - 2 * dx
+    moved = (r.random(n) < frac) & ((pos >= lo) & (pos <= hi)).all(1)
+    pos2 = pos.copy()
+    pos2[moved] += (r.random((moved.sum(), 3)).astype(np.float32) - 0.5) * reach * dx
+    order = mt.order.cpu().numpy()
+    aos = torch.empty(n, mt.nchn, dtype=torch.float32, device=mt.buf.device)
+    lib().zs_rocm_tv_to_aos_f32(mt.pol.handle, mt.buf.data_ptr(), n, mt.nchn, mt.L, aos.data_ptr())
+    mt.pol.syncCtx()
+    aos[:, 1:4] = torch.from_numpy(pos2[order]).to(aos.device)
+    lib().zs_rocm_tv_from_aos_f32(mt.pol.handle, aos.data_ptr(), n, mt.nchn, mt.L, mt.buf.data_ptr())
+    mt.pol.syncCtx()
+    return pos2, moved
+
+
+def oracle_stress(oracle, om, Cm, F, logJp=None):
+    """[n, 9] P F^T vol of every particle as orc_mpm_p2g's model_contrib computes it (before the -dt D_inv scale), from copies of the
+    inputs; the fluid's (model 4, J in F[:, 0]) restated in numpy float32 in the same operation order (the oracle builds without
+    FP contraction)."""
+    p = om.p
+    n = F.shape[0]
+    out = np.zeros((n, 9), np.float32)
+    cf = C.c_float
+    if p.model == 4:
+        f = np.float32
+        J = F[:, 0].astype(np.float32)
+        vol = f(p.volume) * J
+        J2 = J * J
+        J4 = J2 * J2
+        pressure = f(p.bulk) * (f(1) / (J * J2 * J4) - f(1))
+        Cf = Cm.astype(np.float32)
+        vis = f(p.viscosity)
+        for r in range(3):
+            for c in range(3):
+                d = r + 3 * c
+                s = (Cf[:, d] + Cf[:, c + 3 * r]) * vis
+                out[:, d] = ((s - pressure) if r == c else s) * vol
+        return out
+    mu, lam = cf(), cf()
+    oracle.orc_lame(cf(p.E), cf(p.nu), C.byref(mu), C.byref(lam))
+    oracle.orc_nacc_bulk.restype = cf
+    lj = np.zeros(n, np.float32) if logJp is None else logJp.astype(np.float32).copy()
+    for i in range(n):
+        Fi = np.ascontiguousarray(F[i], np.float32).copy()
+        if p.model == 0:
+            oracle.orc_stress_fixedcorotated(cf(p.volume), mu, lam, ptr(Fi), ptr(out[i]))
+        elif p.model == 2:
+            oracle.orc_stress_vonmises(cf(p.volume), mu, lam, cf(p.yieldStress), p.hostVariant, ptr(Fi), ptr(out[i]))
+        elif p.model == 1:
+            l = cf(lj[i])
+            oracle.orc_stress_sand(cf(p.volume), mu, lam, cf(p.cohesion), cf(p.beta), cf(p.yieldSurface), p.volCorrection, C.byref(l),
+                                   ptr(Fi), ptr(out[i]))
+        else:
+            l = cf(lj[i])
+            oracle.orc_stress_nacc(cf(p.volume), mu, lam, cf(oracle.orc_nacc_bulk(cf(p.E), cf(p.nu))), cf(p.xi), cf(p.beta), cf(p.Msqr),
+                                   p.hardeningOn, p.hostVariant, C.byref(l), ptr(Fi), ptr(out[i]))
+    return out
+
+
 def lbvh_boxes(n, seed, dup=False):
     """n AABBs [n][6] = {min xyz, max xyz}: jittered centres in the unit cube, extents 0.5-3 % (dup: centres snapped to a
     coarse lattice so that many morton codes coincide)."""
