@@ -1,7 +1,7 @@
 """Float64 reference of the particle <-> grid transfers with a node-local (and particle-local) error bound.
 
 The transfers have an exact answer: given the float32 inputs and the kernel's own float32 discrete decisions (the base node and the
-d0 of the quadratic B-spline, `make_arena` in zpc_amd/csrc/mpm_device.hpp), weights, scatter, gather, grid update and the F update
+d0 of the quadratic B-spline, `make_arena` in zpc_amd/csrc/mpm_particles.hpp), weights, scatter, gather, grid update and the F update
 involve no approximation.  So every node and every particle is checked against its own bound
 
     |got - ref| <= (N + c) * u * T + e_in + (N + c) * 2^-126
@@ -170,7 +170,7 @@ def p2g64(mass, pos, vel, C, dx, dt, PF=None, ev=None, eC=None, ePF=None):
 
 def eos_pf64(J, bulk, volume):
     """the fluid's P F^T vol without viscosity, -bulk (J^-7 - 1) volume J I, as [n, 9], and its float32 error bound (stress_eos,
-    mpm_device.hpp): J^7 from J2, J4 and two products (6 u), the reciprocal (7 u of J^-7), then - 1, * bulk, volume * J and * vol one
+    mpm_math.hpp): J^7 from J2, J4 and two products (6 u), the reciprocal (7 u of J^-7), then - 1, * bulk, volume * J and * vol one
     rounding each: <= 11 u of bulk volume |J| (J^-7 + 1) on the diagonal, 0 off it"""
     J = np.asarray(J, np.float64)
     b, vol = float(np.float32(bulk)), float(np.float32(volume))

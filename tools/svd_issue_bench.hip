@@ -1,9 +1,9 @@
 // How fast does a SIMD of gfx950 issue REAL per-lane code -- the product's 3x3 SVD + Drucker-Prager return mapping (svd3_core, stress_sand of
-// zpc_amd/csrc/mpm_device.hpp), registers only, no memory -- against the number of resident waves?  tools/valu_issue_bench.hip: independent
+// zpc_amd/csrc/mpm_math.hpp), registers only, no memory -- against the number of resident waves?  tools/valu_issue_bench.hip: independent
 // v_fma_f32 issue every 2.2 cycles per SIMD once two waves are resident (one wave alone: 4.6).  The fused step averages 4.1 cycles per VALU
 // instruction per SIMD with four resident waves; this bench tells how much of that is the instruction mix itself.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -I include -I zpc_amd/csrc tools/svd_issue_bench.hip -o tools/bin/svd_issue_bench
-#include "../zpc_amd/csrc/mpm_device.hpp"
+#include "../zpc_amd/csrc/mpm_math.hpp"
 #include <cstdio>
 using namespace zsr;
 

@@ -1,5 +1,350 @@
-// mpm.hip -- partition, index buckets, binning, grid update, constitutive test entries, owner classification, halo pack/unpack (see mpm_device.hpp for the kernels)
-#include "mpm_device.hpp"
+// mpm.hip -- partition, index buckets, binning, grid update, constitutive test entries, owner classification, halo pack/unpack: kernels and entry points.
+// Replaces, behind include/zs_rocm.h:
+//   ComputeSparsity / EnlargeSparsity        simulation/sparsity/SparsityOp.hpp:59-115
+//   ComputeGridBlockVelocity                 simulation/grid/GridOp.hpp:71-108
+#include "hashtable.hpp"
+#include "mpm_update_stress_kernel.hpp"
+
+namespace zsr {
+
+void exclusive_scan_u32(Launch &L, const unsigned *in, size_t n, unsigned *out);
+void radix_sort_pair_u32(Launch &L, const unsigned *kin, const int *vin, unsigned *kout, int *vout, size_t n, int sbit, int ebit);
+
+// ======================================================================================= sparsity
+static __global__ __launch_bounds__(256) void compute_sparsity_kernel(BhtDev t, Port<float> pos, size_t n, float dxinv, int side, int kscale) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < n;
+  int b[3] = {0, 0, 0};
+  if (valid) {
+    float p[3];
+    load_attr<3>(pos, i, p);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) b[d] = floordiv((int)floorf(p[d] * dxinv + 0.5f) + (-2), side) * kscale;
+  }
+  // neighbouring lanes usually carry the same block: let only the first lane of a run insert (the others
+  // would get sentinel_v back from insert anyway)
+  const int px = shfl_up(b[0], 1), py = shfl_up(b[1], 1), pz = shfl_up(b[2], 1);
+  const bool pvalid = shfl_up((int)valid, 1) != 0;
+  const bool dup = lane_id() != 0 && pvalid && px == b[0] && py == b[1] && pz == b[2];
+  if (valid && !dup) bht_insert<3>(t, b);
+}
+static __global__ __launch_bounds__(256) void enlarge_sparsity_kernel(BhtDev t, int nblocks, int lo0, int lo1, int lo2, int e0, int e1, int e2, int kscale) {
+  // thread per (block, offset)
+  const int per = e0 * e1 * e2;
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)nblocks * per) return;
+  const int i = (int)(g / per), o = (int)(g % per);
+  const int dx = lo0 + o / (e1 * e2), dy = lo1 + (o / e2) % e1, dz = lo2 + o % e2;
+  int k[3] = {t.activeKeys[3 * (size_t)i] + dx * kscale, t.activeKeys[3 * (size_t)i + 1] + dy * kscale, t.activeKeys[3 * (size_t)i + 2] + dz * kscale};
+  bht_insert<3>(t, k);
+}
+// the same functors on a zs::HashTable<i32,3,int> (simulation/sparsity/SparsityOp.hpp:59-115 are written against HashTableView)
+static __global__ __launch_bounds__(256) void compute_sparsity_ht_kernel(HtDev t, Port<float> pos, size_t n, float dxinv, int side) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < n;
+  int b[3] = {0, 0, 0};
+  if (valid) {
+    float p[3];
+    load_attr<3>(pos, i, p);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) b[d] = floordiv((int)floorf(p[d] * dxinv + 0.5f) + (-2), side);
+  }
+  const int px = shfl_up(b[0], 1), py = shfl_up(b[1], 1), pz = shfl_up(b[2], 1);
+  const bool pvalid = shfl_up((int)valid, 1) != 0;
+  const bool dup = lane_id() != 0 && pvalid && px == b[0] && py == b[1] && pz == b[2];
+  if (valid && !dup) ht_insert<3>(t, b);
+}
+static __global__ __launch_bounds__(256) void enlarge_sparsity_ht_kernel(HtDev t, int nblocks, int lo0, int lo1, int lo2, int e0, int e1, int e2) {
+  const int per = e0 * e1 * e2;
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)nblocks * per) return;
+  const int i = (int)(g / per), o = (int)(g % per);
+  int k[3] = {t.activeKeys[3 * (size_t)i] + lo0 + o / (e1 * e2), t.activeKeys[3 * (size_t)i + 1] + lo1 + (o / e2) % e1,
+              t.activeKeys[3 * (size_t)i + 2] + lo2 + o % e2};
+  ht_insert<3>(t, k);
+}
+// index_buckets_for_particles (simulation/particle/Query.tpp:9-58): ComputeSparsity with blockLen 1 / offset 0, then
+// SpatiallyCount (sparsity/SparsityOp.hpp:117-152)
+static __global__ __launch_bounds__(256) void ib_cells_kernel(HtDev t, Port<float> pos, size_t n, float dxinv, float displacement, int *full) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < n;
+  int b[3] = {0, 0, 0};
+  if (valid) {
+    float p[3];
+    load_attr<3>(pos, i, p);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) b[d] = (int)floorf(p[d] * dxinv + displacement);
+  }
+  const int px = shfl_up(b[0], 1), py = shfl_up(b[1], 1), pz = shfl_up(b[2], 1);
+  const bool pvalid = shfl_up((int)valid, 1) != 0;
+  const bool dup = lane_id() != 0 && pvalid && px == b[0] && py == b[1] && pz == b[2];
+  if (valid && !dup && ht_insert<3>(t, b) == HT_FAIL) *full = 1;  // table too small for the occupied cells: the host grows it and retries
+}
+static __global__ __launch_bounds__(256) void ib_count_kernel(HtDev t, Port<float> pos, size_t n, float dxinv, float displacement, unsigned *counts,
+                                                       unsigned *cellOf, int *ids) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float p[3];
+  load_attr<3>(pos, i, p);
+  int b[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) b[d] = (int)floorf(p[d] * dxinv + displacement);
+  int c = ht_query<3>(t, b);
+  if (c < 0) c = *t.cnt;  // not in the table (cannot happen after a successful cell pass): the spare last bucket, never out of bounds
+  cellOf[i] = (unsigned)c;
+  ids[i] = (int)i;
+  atomicAdd(&counts[c], 1u);
+}
+// buckets over the cells of a block partition (zs_rocm_index_buckets_for_partition): bucket = block * side^3 + cell id of the cell
+// that contains the particle; particles whose cell is not in the partition go to the extra bucket `nbuckets`
+static __global__ __launch_bounds__(256) void ib_dense_count_kernel(BhtDev t, Port<float> pos, size_t n, float dxinv, int side, int kscale,
+                                                             int nbuckets, unsigned *counts, unsigned *cellOf, int *ids) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float p[3];
+  load_attr<3>(pos, i, p);
+  int key[3], loc[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const int c = (int)floorf(p[d] * dxinv);
+    loc[d] = c & (side - 1);
+    key[d] = (c - loc[d]) / side * kscale;
+  }
+  const int b = bht_query<3>(t, key);
+  const int bucket = b < 0 ? nbuckets : b * side * side * side + (loc[0] * side + loc[1]) * side + loc[2];
+  cellOf[i] = (unsigned)bucket;
+  ids[i] = (int)i;
+  atomicAdd(&counts[bucket], 1u);
+}
+static __global__ __launch_bounds__(256) void build_neighbors_kernel(BhtDev t, int nblocks, int *nbr, int kscale) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)nblocks * 8) return;
+  const int i = (int)(g >> 3), o = (int)(g & 7);
+  int k[3] = {t.activeKeys[3 * (size_t)i] + (o >> 2) * kscale, t.activeKeys[3 * (size_t)i + 1] + ((o >> 1) & 1) * kscale,
+              t.activeKeys[3 * (size_t)i + 2] + (o & 1) * kscale};
+  nbr[g] = bht_query<3>(t, k);
+}
+
+// ======================================================================================= binning
+template <int SIDE>
+static __global__ __launch_bounds__(256) void bin_count_kernel(BhtDev t, Port<float> pos, size_t n, float dx, unsigned *cellCount,
+                                                        unsigned *cellOf, unsigned *rankOf, int *err, int kscale) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float p[3];
+  load_attr<3>(pos, i, p);
+  int key[3], loc[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const int c = (int)floorf(p[d] * (1.0f / dx) - 0.5f);
+    loc[d] = c & (SIDE - 1);
+    key[d] = (c - loc[d]) / SIDE * kscale;
+  }
+  const int b = bht_query<3>(t, key);
+  if (b < 0) {
+    *err = 1;
+    cellOf[i] = 0xffffffffu;
+    return;
+  }
+  const int sub = SIDE == 4 ? 0 : (((loc[0] >> 2) * 2 + (loc[1] >> 2)) * 2 + (loc[2] >> 2));
+  const unsigned cell = ((unsigned)b * bins_per_block<SIDE>() + sub) * 64u +
+                        (unsigned)(((loc[0] & 3) * 4 + (loc[1] & 3)) * 4 + (loc[2] & 3));
+  cellOf[i] = cell;
+  rankOf[i] = atomicAdd(&cellCount[cell], 1u);
+}
+static __global__ __launch_bounds__(256) void bin_place_kernel(size_t n, const unsigned *cellStart, const unsigned *cellOf,
+                                                        const unsigned *rankOf, int *byCell) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned c = cellOf[i];
+  if (c != 0xffffffffu) byCell[cellStart[c] + rankOf[i]] = (int)i;
+}
+// one wave per bin, lane = cell: (cell, rank) order -> (rank, cell) order.  The ranks handed out by the counting pass are in
+// arrival order of its atomics; the lane first sorts its cell's particle ids (odd-even transposition network in registers,
+// K = 8 / 16 / 32 chosen per bin), so that within a cell the particles keep their previous relative order: a particle that
+// did not change cell stays in "its" round, and the permutation of a re-ordering fused step is the identity except around the
+// movers (coalesced reads through `order`).
+template <int K>
+__device__ __forceinline__ void bin_rr_emit(unsigned cnt, unsigned st, const int *byCell, int *order, unsigned &base, unsigned long long lt) {
+  int ids[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) ids[k] = (unsigned)k < cnt ? byCell[st + k] : 0x7fffffff;
+#pragma unroll
+  for (int pass = 0; pass < K; ++pass)
+#pragma unroll
+    for (int k = pass & 1; k + 1 < K; k += 2) {
+      const int a = ids[k], b = ids[k + 1];
+      ids[k] = a < b ? a : b;
+      ids[k + 1] = a < b ? b : a;
+    }
+#pragma unroll
+  for (int r = 0; r < K; ++r) {
+    const bool has = cnt > (unsigned)r;
+    const unsigned long long m = __ballot(has);
+    if (!m) return;
+    if (has) order[base + (unsigned)__popcll(m & lt)] = ids[r];
+    base += (unsigned)__popcll(m);
+  }
+}
+static __global__ __launch_bounds__(64) void bin_roundrobin_kernel(int nbins, const unsigned *cellStart, const unsigned *cellCount,
+                                                            const int *byCell, int *order, int *binStart, unsigned total) {
+  const int bin = blockIdx.x, c = threadIdx.x;
+  const unsigned cnt = cellCount[(size_t)bin * 64 + c], st = cellStart[(size_t)bin * 64 + c];
+  unsigned base = shfl(st, 0);
+  if (c == 0) {
+    binStart[bin] = (int)base;
+    if (bin == nbins - 1) binStart[nbins] = (int)total;
+  }
+  const unsigned long long lt = lanemask_lt();
+  unsigned mx = cnt;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned o = shfl_down(mx, d);
+    mx = o > mx ? o : mx;
+  }
+  mx = shfl(mx, 0);
+  if (mx <= 8u) bin_rr_emit<8>(cnt, st, byCell, order, base, lt);
+  else if (mx <= 16u) bin_rr_emit<16>(cnt, st, byCell, order, base, lt);
+  else bin_rr_emit<32>(cnt, st, byCell, order, base, lt);
+  for (unsigned r = 32;; ++r) {  // cells with more than 32 particles: the rest in arrival order
+    const bool has = cnt > r;
+    const unsigned long long m = __ballot(has);
+    if (!m) break;
+    if (has) order[base + (unsigned)__popcll(m & lt)] = byCell[st + r];
+    base += (unsigned)__popcll(m);
+  }
+}
+
+// ======================================================================================= grid update
+template <int SIDE>
+static __global__ __launch_bounds__(256) void grid_update_kernel(float *grid, size_t nblocks, float dt, float e0, float e1, float e2,
+                                                          float *maxVelSqr) {
+  constexpr int NC = SIDE * SIDE * SIDE;
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float vsq = 0.f;
+  if (g < nblocks * NC) {
+    const size_t b = g / NC, c = g % NC;
+    float *blk = grid + b * 7 * NC + c;
+    float mass = blk[0];
+    if (mass != 0.f) {
+      mass = 1.f / mass;
+      const float v0 = blk[1 * NC] * mass + e0 * dt, v1 = blk[2 * NC] * mass + e1 * dt, v2 = blk[3 * NC] * mass + e2 * dt;
+      blk[1 * NC] = v0;
+      blk[2 * NC] = v1;
+      blk[3 * NC] = v2;
+      vsq = v0 * v0 + v1 * v1 + v2 * v2;
+    }
+  }
+  if (maxVelSqr) {  // atomic_max(maxVel, |v|^2) (GridOp.hpp:103-104): workgroup max, then at most one int-ordered atomic
+    // One device-wide word takes ~90 atomics per microsecond: an atomic per wave of a 27 200-block grid (217 k of them) cost 2.4 ms.
+    // The maximum only grows, so a workgroup first looks at the current value and stays silent unless it can raise it.
+    __shared__ float wmax[4];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) vsq = fmaxf(vsq, shfl_down(vsq, d));
+    if (lane_id() == 0) wmax[wave_id()] = vsq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+      if (m > 0.f && __float_as_int(m) > __hip_atomic_load((int *)maxVelSqr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMax((int *)maxVelSqr, __float_as_int(m));
+    }
+  }
+}
+
+// ======================================================================================= misc kernels
+template <int MODEL> __global__ void stress_kernel(MpmDev mp, float *F, float *logJp, size_t n, float *PF) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float f[9], pf[9];
+#pragma unroll
+  for (int d = 0; d < 9; ++d) f[d] = F[9 * i + d];
+  float lj = 0.f;
+  if constexpr (model_uses_logjp(MODEL)) lj = logJp[i];
+  const float C0[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // the fluid's viscous part needs C: zero through this entry
+  model_stress<MODEL, true>(mp.mat, lj, f, pf, C0);
+  if constexpr (model_uses_logjp(MODEL)) logJp[i] = lj;
+  if constexpr (MODEL != ZS_MPM_FIXED_COROTATED) {  // the plastic models return the projected F
+#pragma unroll
+    for (int d = 0; d < 9; ++d) F[9 * i + d] = f[d];
+  }
+#pragma unroll
+  for (int d = 0; d < 9; ++d) PF[9 * i + d] = pf[d];
+}
+static __global__ void svd_kernel(const float *F, size_t n, float *U, float *S, float *V) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float f[9], u[9], s[3], v[9];
+#pragma unroll
+  for (int d = 0; d < 9; ++d) f[d] = F[9 * i + d];
+  svd3(f, u, s, v);
+#pragma unroll
+  for (int d = 0; d < 9; ++d) {
+    U[9 * i + d] = u[d];
+    V[9 * i + d] = v[d];
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) S[3 * i + d] = s[d];
+}
+// owner rank of every particle under the block-aligned box split of zpc_amd/dist.py (cell_box): cell = floor(x / dx) clamped to
+// the global box; along axis d the box [lo, hi) is cut at lo + (n k / dims) rounded down to a multiple of `align`
+struct OwnerSplit {
+  int lo[3], hi[3], dims[3], align;
+};
+static __global__ __launch_bounds__(256) void owner_rank_kernel(Port<float> pos, size_t n, float dxinv, OwnerSplit sp, int *owner) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float p[3];
+  load_attr<3>(pos, i, p);
+  int rc[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    int c = (int)floorf(p[d] * dxinv);
+    c = c < sp.lo[d] ? sp.lo[d] : (c >= sp.hi[d] ? sp.hi[d] - 1 : c);
+    const int len = sp.hi[d] - sp.lo[d];
+    int r = 0;
+    for (int k = 1; k < sp.dims[d]; ++k) {
+      int cut = sp.lo[d] + (int)(((long long)len * k) / sp.dims[d]);
+      cut = floordiv(cut, sp.align) * sp.align;
+      r += c >= cut;
+    }
+    rc[d] = r;
+  }
+  owner[i] = (rc[0] * sp.dims[1] + rc[1]) * sp.dims[2] + rc[2];
+}
+// per-workgroup LDS histogram of the owner ranks, one global atomic per (workgroup, rank that occurs)
+static __global__ __launch_bounds__(256) void owner_count_kernel(const int *owner, size_t n, int world, int *counts) {
+  extern __shared__ int ocHist[];
+  for (int r = threadIdx.x; r < world; r += 256) ocHist[r] = 0;
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const int o = owner[i];
+    if ((unsigned)o < (unsigned)world) atomicAdd(&ocHist[o], 1);
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < world; r += 256)
+    if (ocHist[r]) atomicAdd(&counts[r], ocHist[r]);
+}
+static __global__ void halo_pack_kernel(const float *grid, const int *blocks, size_t nb, int nc, int chn0, int nchn, float *buf) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t per = (size_t)nchn * nc;
+  if (g >= nb * per) return;
+  const size_t i = g / per, r = g % per;
+  buf[g] = grid[((size_t)blocks[i] * 7 + chn0) * nc + r];
+}
+// MODE 0: set, 1: add (each block appears once in `blocks`), 2: atomic add (the list may name a block several times, e.g. the
+// concatenated messages of several peers that all share a corner block)
+template <int MODE> __global__ void halo_unpack_kernel(float *grid, const int *blocks, size_t nb, int nc, int chn0, int nchn, const float *buf) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t per = (size_t)nchn * nc;
+  if (g >= nb * per) return;
+  const size_t i = g / per, r = g % per;
+  float *dst = grid + ((size_t)blocks[i] * 7 + chn0) * nc + r;
+  if constexpr (MODE == 2) unsafeAtomicAdd(dst, buf[g]);
+  else if constexpr (MODE == 1) *dst += buf[g];
+  else *dst = buf[g];
+}
+
+}  // namespace zsr
 
 using namespace zsr;
 

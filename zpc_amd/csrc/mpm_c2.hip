@@ -14,8 +14,9 @@
 //          2. per particle: sum over the cells in range, add to v_p / B_p                              (g2c2p_particle_kernel)
 // Evaluating the plastic models once per particle also removes the reference's order dependence (its functor stores logJp up to 8
 // times per particle and later cells read the updated value).
-#include "mpm_device.hpp"
+#include "bht.hpp"
 #include "hashtable.hpp"
+#include "mpm_particles.hpp"
 
 using namespace zsr;
 

@@ -1,5 +1,6 @@
-// mpm_fused.hip -- fused G2P2G entry points: zs_rocm_mpm_g2p2g_range / zs_rocm_mpm_g2p2g (see mpm_device.hpp for the kernels)
-#include "mpm_device.hpp"
+// mpm_fused.hip -- fused G2P2G entry points: zs_rocm_mpm_g2p2g_range / zs_rocm_mpm_g2p2g (kernels: mpm_fused_kernels.hpp, compiled in
+// mpm_fused4.hip / mpm_fused8.hip through mpm_fused_impl.hpp)
+#include "mpm_fused_common.hpp"
 
 using namespace zsr;
 

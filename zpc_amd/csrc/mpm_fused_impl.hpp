@@ -1,6 +1,6 @@
 // mpm_fused_impl.hpp -- body of g2p2g_launch_side<S> (included by mpm_fused4.hip and mpm_fused8.hip only)
 #pragma once
-#include "mpm_device.hpp"
+#include "mpm_fused_kernels.hpp"
 
 namespace zsr {
 

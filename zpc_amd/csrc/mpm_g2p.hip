@@ -1,5 +1,5 @@
-// mpm_g2p.hip -- G2PTransfer entry point: zs_rocm_mpm_g2p (see mpm_device.hpp for the kernels)
-#include "mpm_device.hpp"
+// mpm_g2p.hip -- G2PTransfer entry point: zs_rocm_mpm_g2p (kernels: mpm_g2p_kernels.hpp)
+#include "mpm_g2p_kernels.hpp"
 
 using namespace zsr;
 

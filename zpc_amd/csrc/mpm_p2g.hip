@@ -1,5 +1,6 @@
-// mpm_p2g.hip -- P2GTransfer entry point: zs_rocm_mpm_p2g (see mpm_device.hpp for the kernels)
-#include "mpm_device.hpp"
+// mpm_p2g.hip -- P2GTransfer entry point: zs_rocm_mpm_p2g (kernels: mpm_p2g_kernels.hpp, mpm_update_stress_kernel.hpp)
+#include "mpm_p2g_kernels.hpp"
+#include "mpm_update_stress_kernel.hpp"
 
 using namespace zsr;
 

@@ -1,7 +1,8 @@
 // mpm_slot.hpp -- device code shared by the kernels of the fused G2P2G step on SLOTTED particle storage (mpm_slotted.hip: one workgroup
 // per bin; mpm_slotblk.hip: one workgroup per 8^3 block, its bins pipelined back to back).  Storage, mover protocol: mpm_slotted.hip.
 #pragma once
-#include "mpm_device.hpp"
+#include "mpm_arena.hpp"
+#include "mpm_fused_common.hpp"
 
 namespace zsr {
 
@@ -11,24 +12,6 @@ constexpr int SL_REC = 48;    // floats per outbox record (192 bytes = three 64-
                               // (round * 64 + cell: where slot_rehome_kernel puts it back when the destination cell has no free round);
                               // then [16] v(3), [19] C(9), [28] P F^T(9) (written for writeAll steps and for flagged records only)
 constexpr int SLR_DCELL = 14, SLR_FLAG = 15, SLR_V = 16, SLR_C = 19, SLR_PF = 28;
-
-#ifdef ZS_SLOT_PROBE  // measurement-only build (tools/ablate_slot.sh PROBE): cycle stamps of a workgroup's phases, summed over sampled workgroups
-static __device__ unsigned long long g_slot_probe[32];
-#define SLP_SAMPLED ((blockIdx.x & 63) == 0)
-#define SLP_T0(name) const unsigned long long name = __builtin_readcyclecounter()
-#define SLP_ADD(slot, t0) do { if ((threadIdx.x & 63) == 0 && SLP_SAMPLED) atomicAdd(&g_slot_probe[slot], (unsigned long long)(__builtin_readcyclecounter() - (t0))); } while (0)
-#define SLP_ACC(var, t0) var += __builtin_readcyclecounter() - (t0)
-#define SLP_PUT(slot, v) do { if ((threadIdx.x & 63) == 0 && SLP_SAMPLED) atomicAdd(&g_slot_probe[slot], (unsigned long long)(v)); } while (0)
-#define SLP_SEG(k) do { if (seg) { const unsigned long long tn_ = __builtin_readcyclecounter(); seg[k] += tn_ - tseg_; tseg_ = tn_; } } while (0)
-#define SLP_SEG0() unsigned long long tseg_ = __builtin_readcyclecounter()
-#else
-#define SLP_T0(name) do { } while (0)
-#define SLP_ADD(slot, t0) do { } while (0)
-#define SLP_ACC(var, t0) do { } while (0)
-#define SLP_PUT(slot, v) do { } while (0)
-#define SLP_SEG(k) do { } while (0)
-#define SLP_SEG0() do { } while (0)
-#endif
 
 struct SlotArgs {
   const float *gridA;
@@ -281,10 +264,8 @@ struct SlotBinView {
 template <int SIDE, int SMODEL, bool WRITE_ALL, class VA, bool INBLK = false, class REC, class WAIT>
 __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const ParticlesDev &ps, const REC &cur, unsigned code0, size_t i0, int lane,
                                                    unsigned spos, float *myStage, const SlotBinView &bv, const SlotArgs &A, unsigned *arrCnt,
-                                                   unsigned short (*arrQ)[SL_ARRQ], unsigned *xCnt, unsigned *xq, WAIT beforeStage,
-                                                   unsigned long long *seg = nullptr) {  // seg: probe builds only (cycles per segment)
+                                                   unsigned short (*arrQ)[SL_ARRQ], unsigned *xCnt, unsigned *xq, WAIT beforeStage) {
   constexpr int LW = 64;
-  SLP_SEG0();
   constexpr bool DP = model_uses_logjp(SMODEL);
   constexpr bool FLUID = model_is_fluid(SMODEL);
   const float dxi = mp.dxi;
@@ -300,7 +281,6 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
   } else {
     float vel[3], C[9];
     g2p_gather_lds<VA>(mp, ar, bv.va + VA::at(ocx, ocy, ocz), D_inv, vel, C);
-    SLP_SEG(0);  // arena set-up + gather
     float pos[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) pos[d] = cur.pos[d] + vel[d] * mp.dt;
@@ -315,7 +295,6 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
       nc[d] = (int)fl - bv.org[d];
       lpn[d] = X - fl;
     }
-    SLP_SEG(1);  // advection, F update, new base node
     const float pm = cur.m;
     float plj = 0.f;
     if constexpr (DP) plj = cur.logJp;
@@ -461,11 +440,9 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
       }
     }
     const bool stored = !moved || home || keep;  // the particle's state is in its own, lowered, new or old slot (else: in its record)
-    SLP_SEG(2);  // tickets / queues / records of the movers, the particle's stores
     {  // the plastic models may project the local copy of F (the stored / recorded F is the unprojected one, P2G.hpp:101)
       float lj = plj;
       model_stress<SMODEL>(mp.mat, lj, F, PF, C);
-      SLP_SEG(3);  // constitutive update
       if (outbox) {
         if (rec) {
           rec[0] = pm;
@@ -486,16 +463,13 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
         if (moved || lowered) pstore1<LW>(ps.mass, o, pm);
       }
     }
-    SLP_SEG(4);  // logJp / stress / mass stores, record tail
     if (staged) {
       // staged AFTER the constitutive update, as in g2p2g_rs_producer: with m, x', v', C' dead before it the compiler
       // reuses their registers for the SVD at once and waits for the particle stores just issued (s_waitcnt vmcnt(1)
       // in front of the SVD: 2 ms per 64 Mi particles)
       valid = !moved && !byList;  // an in-bin mover is consumed by the lane of its NEW cell (arrival queue), not by the lane of its entry
       beforeStage();
-      SLP_SEG(5);  // wait for the ring slot
       stage_qform(mp, myStage, pm, lpn, vel, C, PF);
-      SLP_SEG(6);  // staging
     }
   }
   return valid;
@@ -555,14 +529,8 @@ __device__ __forceinline__ void g2p2g_slot_producer(const MpmDev &mp, const Part
       for (int ch = 0; ch < 3; ++ch) a[ch * AL::CH] = bn >= 0 ? g[ch * NC] : 0.f;
     }
   }
-  SLP_T0(tFill);
   __syncthreads();
-  if (W == 0) SLP_ADD(2, tFill);
-#ifdef ZS_SLOT_PROBE
-  unsigned long long tWork = 0, tBar = 0;
-#endif
   for (int it = 0; it < nchunks; ++it) {
-    SLP_T0(tIt);
     {
       const int grp = 4 * it + W;
       const int par = it % 3;
@@ -590,24 +558,15 @@ __device__ __forceinline__ void g2p2g_slot_producer(const MpmDev &mp, const Part
         if (lane == 0) smask[grp % SL_NG] = vm;
       }
     }
-    SLP_ACC(tWork, tIt);
-    SLP_T0(tB);
     __syncthreads();
-    SLP_ACC(tBar, tB);
   }
   {  // nothing left to produce (the consumers accumulate the rounds of the last chunk): the last chunk's global-atomic list
-    SLP_T0(tB);
     if (nchunks > 0) {  // the list of the last chunk is scattered by the (then idle) producer waves
       const int par = (nchunks - 1) % 3;
       const int nx = xCnt[par] < (unsigned)SL_XQ ? (int)xCnt[par] : SL_XQ;
       slot_xlist_scatter<SIDE, W>(mp, geo, stage, xq[par], nx, lane, sh.nbrBlk, A);
     }
     __syncthreads();
-    if (W == 0) SLP_ADD(6, tB);
-  }
-  if (W == 0) {
-    SLP_PUT(3, tWork);
-    SLP_PUT(4, tBar);
   }
 }
 // consumer wave of channel set CS: lane = cell; after chunk c has been produced every round whose last entry lies below 256 (c + 1)
@@ -633,12 +592,8 @@ __device__ __forceinline__ void g2p2g_slot_consumer(const MpmDev &mp, const BinG
 #pragma unroll
     for (int q = 0; q < S::NA; ++q) acc[k][q] = 0.f;
   __syncthreads();  // (the producers fill the velocity arena meanwhile)
-#ifdef ZS_SLOT_PROBE
-  unsigned long long tWork = 0, tBar = 0;
-#endif
   int r = 0, off = 0;  // next round to consume, entry number of its first particle
   for (int it = 0; it <= nchunks; ++it) {
-    SLP_T0(tIt);
     if (it > 0) {
       const int par = (it - 1) % 3;
       const int produced = 256 * it < total ? 256 * it : total;
@@ -674,30 +629,15 @@ __device__ __forceinline__ void g2p2g_slot_consumer(const MpmDev &mp, const BinG
           spos = (int)(p >> 6) * (G2P2G_QF * 64) + (int)(p & 63u);
         }
         if (spos >= 0) g2p2g_consume_set<CS>(mp, stage, spos, acc);
-        if (CS == 0) SLP_PUT(15, 1);  // [15] consumer: loop iterations (rounds + extra rounds for arrivals)
       }
-      if (CS == 0) SLP_ADD(13, tIt);  // [13] consumer: rounds loop (incl. in-bin arrivals)
-      SLP_T0(tX);
       // movers of the chunk whose new cell is not a lane of this bin (or whose cell's arrival queue was full): slot_xlist_scatter.  The
       // list of the LAST chunk is taken by the producer waves, which have nothing left to produce in that iteration
       const int nx = xCnt[par] < (unsigned)SL_XQ ? (int)xCnt[par] : SL_XQ;
       if (CS == 0 && lane == 0) xCnt[(it + 1) % 3] = 0u;
       if (it < nchunks) slot_xlist_scatter<SIDE, CS>(mp, geo, stage, xq[par], nx, lane, nbrBlk, A);
-      if (CS == 0) {
-        SLP_ADD(14, tX);  // [14] consumer: global-atomic list
-        SLP_PUT(12, nx);  // [12] entries of the list
-      }
     }
-    SLP_ACC(tWork, tIt);
-    SLP_T0(tB);
     __syncthreads();
-    SLP_ACC(tBar, tB);
   }
-  if (CS == 0) {
-    SLP_PUT(7, tWork);
-    SLP_PUT(8, tBar);
-  }
-  SLP_T0(tFl);
   // the set's channels of the bin's arena belong to this wave alone; phases ordered inside the wave (see g2p2g_body)
   // (the arena lives in the staging ring, which nobody reads after the loop's last barrier: cleared here, by the wave that owns the channels)
   for (int k = lane; k < S::NA * AL::CH; k += 64) parena[(size_t)S::CH0 * AL::CH + k] = 0.f;
@@ -710,7 +650,6 @@ __device__ __forceinline__ void g2p2g_slot_consumer(const MpmDev &mp, const BinG
     for (int q = 0; q < S::NA; ++q) g[q * AL::CH] += acc[k][q];
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
-  if (CS == 0) SLP_ADD(9, tFl);
 }
 
 // mpm_slotblk.hip: the step's main kernel for 8^3 blocks, one workgroup per block (blocks [A.binBase / 8, + A.nbins / 8))

@@ -239,20 +239,7 @@ __device__ __forceinline__ void blk_producer(const MpmDev &mp, const ParticlesDe
     }
   }
   __syncthreads();  // every producer has read the first bin's entry table (iteration 0 may rebuild that buffer for the bin of chunk 2)
-#ifdef ZS_SLOT_PROBE
-  unsigned long long tWork = 0, tBar = 0, tRing = 0, tPre = 0, segv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long *const seg = segv;
-  unsigned long long topv[4] = {0, 0, 0, 0}, tTop = 0;
-#define SLP_TOP(k) do { const unsigned long long tn_ = __builtin_readcyclecounter(); topv[k] += tn_ - tTop; tTop = tn_; } while (0)
-#else
-#define SLP_TOP(k) do { } while (0)
-  unsigned long long *const seg = nullptr;
-#endif
   for (int g = 0; g < G; ++g) {
-    SLP_T0(tIt);
-#ifdef ZS_SLOT_PROBE
-    tTop = tIt;
-#endif
     ChunkDesc d[3];  // chunks g - 1, g, g + 1
     blk_chunk_descs(sh.desc, g, d);
     const int b = d[1].bin();
@@ -263,7 +250,6 @@ __device__ __forceinline__ void blk_producer(const MpmDev &mp, const ParticlesDe
     has0 = has1;
     code0 = code1;
     has1 = false;
-    SLP_TOP(0);  // descriptors, hand-over
     if (g + 1 < G) {  // the records of the next chunk (this bin's or the next bin's): in flight during this chunk
       const int b1 = d[2].bin();
       const int j1 = 256 * d[2].idx() + 64 * W + lane;
@@ -273,7 +259,6 @@ __device__ __forceinline__ void blk_producer(const MpmDev &mp, const ParticlesDe
         nxt.load(ps, elem(b1, code1));
       }
     }
-    SLP_TOP(1);  // record requests
     // (per-bin state around the bin boundaries -- a finished bin's counters, the next bins' entry tables and neighbour bins -- is kept by the
     // consumer waves, which have the time: see blk_consumer)
     const SubGeom sg = sub_geom(borg, b);
@@ -287,44 +272,17 @@ __device__ __forceinline__ void blk_producer(const MpmDev &mp, const ParticlesDe
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
     bool valid = false;
-    SLP_ACC(tPre, tIt);
     if (has0)
       valid = slot_produce_entry<8, SMODEL, WRITE_ALL, ArenaBlk, true>(mp, ps, cur, code0, elem(b, code0), lane, (unsigned)(slot * 64 + lane), myStage + lane, bv, A,
-                                                                 sh.arrCnt[par], sh.arrQ[par], &sh.xCnt[par], sh.xq[par], ringFree, seg);
-    SLP_T0(tR);
+                                                                 sh.arrCnt[par], sh.arrQ[par], &sh.xCnt[par], sh.xq[par], ringFree);
     ringFree();
-    SLP_ACC(tRing, tR);
     {
       const unsigned long long vm = __ballot(valid);
       if (lane == 0) sh.smask[slot] = vm;
     }
-    SLP_ACC(tWork, tIt);
-#ifdef ZS_SLOT_PROBE
-    {  // how long do the acknowledgements of this iteration's stores (and the next chunk's records) take from here?
-      SLP_T0(tV);
-      __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
-      SLP_ACC(segv[7], tV);
-    }
-#endif
-    SLP_T0(tB);
     __syncthreads();  // chunk g is staged
-    SLP_ACC(tBar, tB);
   }
-  SLP_T0(tF);
   __syncthreads();  // the consumers have accumulated the last chunk and flushed the last bin
-  if (W == 0) {
-    SLP_ADD(6, tF);
-    SLP_PUT(3, tWork);
-    SLP_PUT(4, tBar);
-    SLP_PUT(2, tRing);
-    SLP_PUT(5, G);
-#ifdef ZS_SLOT_PROBE
-    SLP_PUT(16, tPre);
-    for (int k = 0; k < 7; ++k) SLP_PUT(17 + k, segv[k]);
-    SLP_PUT(24, segv[7]);
-    for (int k = 0; k < 2; ++k) SLP_PUT(25 + k, topv[k]);
-#endif
-  }
 }
 
 // consumer wave of channel set CS: lane = cell of the current bin; chunk g is consumed while the producers work on chunk g + 1
@@ -363,14 +321,8 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
     blk_chunk_descs(sh.desc, -1 + 1, d);  // chunks -1 .. 3
     binState(-1, d[2], d[3]);
   }
-#ifdef ZS_SLOT_PROBE
-  unsigned long long tWork = 0, tBar = 0, tFlush = 0;
-#endif
   for (int g = 0; g < G; ++g) {
-    SLP_T0(tB);
     __syncthreads();  // chunk g is staged
-    SLP_ACC(tBar, tB);
-    SLP_T0(tIt);
     ChunkDesc d[5];  // chunks g - 1 .. g + 3
     blk_chunk_descs(sh.desc, g, d);
     const int b = d[1].bin(), c = d[1].idx(), total = d[1].total(), par = g % 3;
@@ -426,8 +378,6 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
     if (lane == 0) atomicAdd(sh.done, 1u);
     binState(g, d[3], d[4]);
     if (CS == 3 && d[1].last()) blk_finish_bin(sh, A, blk * 8, b, d[1].qp(), lane);
-    SLP_ACC(tWork, tIt);
-    SLP_T0(tFl);
     if (d[1].last()) {
       // last chunk of the bin: the set's channels of the bin's arena belong to this wave alone -- add the 27 register planes on top of
       // the lists' terms (phases ordered inside the wave), send the arena's nodes to the grid; no other wave is involved
@@ -462,16 +412,8 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the arena is cleared again for the next bin only after these reads)
     }
-    SLP_ACC(tFlush, tFl);
   }
-  SLP_T0(tE);
   __syncthreads();  // the last bin is flushed
-  if (CS == 0) {
-    SLP_PUT(7, tWork);
-    SLP_PUT(8, tBar);
-    SLP_PUT(9, tFlush);
-    SLP_ADD(10, tE);
-  }
 }
 
 template <int SMODEL, bool WRITE_ALL>
@@ -498,7 +440,6 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int blk = (int)blockIdx.x + A.binBase / 8;
   const int bin0 = blk * 8;
-  SLP_T0(tStart);
   // occupancy of the block's 8 bins: wave w <-> bin w
   const unsigned mask = A.cellMask[(size_t)(bin0 + w) * 64 + lane];
   s_masks[w][lane] = mask;
@@ -577,7 +518,6 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
     }
   }
   __syncthreads();
-  if (w == 0) SLP_ADD(1, tStart);
   if (w < 4) blk_producer<SMODEL, WRITE_ALL>(mp, ps, borg, blk, lane, G, sh, A, __builtin_amdgcn_readfirstlane(w));
   else {
     if (w == 4) blk_consumer<0>(mp, borg, blk, lane, G, sh, A);
@@ -590,10 +530,6 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
      // High half of the claim word: slot_rehome_kernel puts the arrivals from other blocks above them (low half)
     const unsigned nl = s_arrLocal[w][lane];
     if (nl) A.claim[(size_t)(bin0 + w) * 64 + lane] = nl << 16;
-  }
-  if (w == 0) {
-    SLP_ADD(0, tStart);
-    SLP_PUT(11, 1);
   }
   if (tid == 0) {
     // movers sent / re-homed: running sums spread over SL_NCTR words (one device-wide word serves ~90 atomics per microsecond)
@@ -652,14 +588,3 @@ void launch_g2p2g_slotblk(hipStream_t stream, int model, bool writeAll, const Mp
 }
 
 }  // namespace zsr
-
-#if defined(ZS_SLOT_PROBE) && defined(ZS_SLOT_PROBE_BLK)  // measurement-only build: read (and clear) the phase stamps of g2p2g_slotblk_kernel
-extern "C" void zs_rocm_slot_probe(unsigned long long *out16, int reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out16, HIP_SYMBOL(zsr::g_slot_probe), sizeof(unsigned long long) * 32);  // (the block kernel's reader: 32 slots)
-  if (reset) {
-    unsigned long long z[32] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(zsr::g_slot_probe), z, sizeof(z));
-  }
-}
-#endif

@@ -29,6 +29,8 @@
 
 namespace zsr {
 
+void exclusive_scan_u32(Launch &L, const unsigned *in, size_t n, unsigned *out);
+
 // ------------------------------------------------------------------------------------------------------------------ slotting
 template <int SIDE>
 static __global__ __launch_bounds__(256) void slot_assign_kernel(BhtDev t, Port<float> pos, size_t n, float dx, unsigned *cellCount, int K,
@@ -137,7 +139,6 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slot_kernel(MpmDev mp, Pa
                       s_xCnt, s_xq, &s_outCount, &s_sent, &s_homed, &s_xOver};
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int bin = (int)blockIdx.x + A.binBase;
-  SLP_T0(tStart);
   const unsigned mask = A.cellMask[(size_t)bin * 64 + lane];
   // round-major enumeration of the occupied slots (every wave walks the rounds; wave w fills the table rows of rounds = w mod 8)
   unsigned any = mask;
@@ -177,7 +178,6 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slot_kernel(MpmDev mp, Pa
     s_nbrBin[code] = code == 13 ? bin : neighbour_bin<SIDE>(A.nbr27, geo.block, bin, code);
   }
   __syncthreads();  // the table is complete
-  if (w == 0) SLP_ADD(1, tStart);
   if (w == 0) g2p2g_slot_producer<SIDE, SMODEL, WRITE_ALL, 0>(mp, ps, geo, bin, total, lane, nchunks, sh, A);
   else if (w == 1) g2p2g_slot_producer<SIDE, SMODEL, WRITE_ALL, 1>(mp, ps, geo, bin, total, lane, nchunks, sh, A);
   else if (w == 2) g2p2g_slot_producer<SIDE, SMODEL, WRITE_ALL, 2>(mp, ps, geo, bin, total, lane, nchunks, sh, A);
@@ -188,7 +188,6 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slot_kernel(MpmDev mp, Pa
     else if (w == 6) g2p2g_slot_consumer<SIDE, 2>(mp, geo, mask, total, lane, nchunks, sh, A);
     else g2p2g_slot_consumer<SIDE, 3>(mp, geo, mask, total, lane, nchunks, sh, A);
   }
-  SLP_T0(tTail);
   __syncthreads();  // all channel sets are in the arena
   if (tid < 64) {  // this step's departures and in-bin arrivals of the bin's cells, for slot_rehome_kernel / slot_commit_kernel
     const unsigned c = s_clr[tid], nl = s_arrLocal[tid];
@@ -233,11 +232,6 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slot_kernel(MpmDev mp, Pa
       outbox_scatter_global<SIDE>(mp, geo, s_stage, nb, w, lane, s_nbrBlk, A.gridB, A.status);
       __syncthreads();
     }
-  }
-  if (w == 0) {
-    SLP_ADD(10, tTail);
-    SLP_ADD(0, tStart);
-    SLP_PUT(11, 1);
   }
 }
 
@@ -397,17 +391,6 @@ static __global__ __launch_bounds__(256) void reslot_grid_kernel(const int *map,
 using namespace zsr;
 
 extern "C" {
-
-#if defined(ZS_SLOT_PROBE) && !defined(ZS_SLOT_PROBE_BLK)  // measurement-only build: read (and clear) the phase stamps of g2p2g_slot_kernel
-void zs_rocm_slot_probe(unsigned long long *out16, int reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out16, HIP_SYMBOL(zsr::g_slot_probe), sizeof(unsigned long long) * 16);
-  if (reset) {
-    unsigned long long z[16] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(zsr::g_slot_probe), z, sizeof(z));
-  }
-}
-#endif
 
 size_t zs_rocm_mpm_slot_outbox_bytes(size_t nbins, int cap, int which) {
   if (which == 0) return nbins * sizeof(int);                              // moverCount

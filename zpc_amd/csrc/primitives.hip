@@ -1129,14 +1129,9 @@ __device__ __forceinline__ void rs_coop_lsd(RsLds<K, PAIR> &S, const K *src, con
 
 // One bucket of c <= MAXI * 1024 keys: into registers (positions stay (wave, item, lane)-ordered), LSD passes over the bits [sbit, top)
 // through LDS, out.
-#ifdef ZS_RS_NOINLINE  // repro builds only (tools/repro/): a real call with a stack in the finish kernel, one of the two r03 builds behind the "scratch trap"
-#define ZS_RS_BUCKET_INLINE __noinline__
-#else
-#define ZS_RS_BUCKET_INLINE __forceinline__
-#endif
 template <class K, bool PAIR, int MAXI>
-__device__ ZS_RS_BUCKET_INLINE void rs_finish_bucket(unsigned (*cnt)[256], unsigned *sWave2, K *keyS, int *valS, const K *bk, const int *bv, K *ok,
-                                                 int *ov, unsigned c, int sbit, int top) {
+__device__ __forceinline__ void rs_finish_bucket(unsigned (*cnt)[256], unsigned *sWave2, K *keyS, int *valS, const K *bk, const int *bv, K *ok,
+                                             int *ov, unsigned c, int sbit, int top) {
   constexpr int NW = RSS_NW, BLOCK = RSS_BLOCK;
   const int lane = lane_id(), w = wave_id(), t = threadIdx.x;
   const int KI = (int)((c + BLOCK - 1) / BLOCK);
@@ -1232,13 +1227,6 @@ __global__ __launch_bounds__(RSS_BLOCK) void radix_small_finish_kernel(const K *
   RsLds<K, PAIR> &S = *reinterpret_cast<RsLds<K, PAIR> *>(ldsRaw);
   FinLds &F = *reinterpret_cast<FinLds *>(ldsRaw);
   const int lane = lane_id(), w = wave_id(), t = threadIdx.x;
-#ifdef ZS_RS_FORCE_SCRATCH  // measurement builds only (tools/repro/): makes this kernel use private memory, see DESIGN "a trap met on the way"
-  {
-    volatile unsigned junk[ZS_RS_FORCE_SCRATCH];
-    for (int i = 0; i < ZS_RS_FORCE_SCRATCH; ++i) junk[(i + threadIdx.x) % ZS_RS_FORCE_SCRATCH] = (unsigned)i;
-    if (junk[threadIdx.x % ZS_RS_FORCE_SCRATCH] == 0xFFFFFFFFu) ctl[RS_CTL_WORDS - 1] = 1u;
-  }
-#endif
   const unsigned mode = ctl[RS_CTL_MODE];
   const int top = (int)ctl[RS_CTL_TOP];
   const unsigned start0 = ctl[blockIdx.x], end0 = ctl[blockIdx.x + 1];  // (gridDim.x <= 256) this workgroup's first bucket, fetched with the mode
