@@ -641,6 +641,54 @@ ZS_ROCM_EXPORT int zs_rocm_mpm_g2c2p_step(zs_rocm_policy *, const zs_rocm_mpm_pa
 ZS_ROCM_EXPORT void zs_rocm_mpm_g2p(zs_rocm_policy *, const zs_rocm_mpm_params *, zs_rocm_particles,
                                     const zs_rocm_bht_3 *, const float *grid, size_t nblocks, const int *binStart,
                                     const unsigned *cellCount, const int *nbr);
+/* ---- the implicit-MPM system (zpc_amd/csrc/mpm_implicit.hip, mpm_implicit_project.hip).
+ * NAMING: the reference's `G2P2GTransfer` functor is the operator below -- internal grid forces at a TRIAL grid velocity, no particle
+ * attribute written.  The `zs_rocm_mpm_g2p2g*` entry points further down are something else: the fused EXPLICIT step (G2P of step n +
+ * P2G of step n + 1, particles advected and stored).
+ * Dof vectors are plain float device arrays [nblocks * side^3][3]: entry 3 * (block * side^3 + cell) + d, the layout of
+ * dof_view<space, 3>(Vector<float>) (G2P2G.hpp:71,135-139).  Particles in compact (unslotted) storage.  Every int-returning call
+ * validates its arguments first and returns -1 with nothing written, else 0. */
+/* pol(range(n), G2P2GTransfer{apic, dt, model, grid, vIn, fOut, table, particles}) (simulation/transfer/G2P2G.hpp:14-150): per particle
+ * C from vIn on the stencil of the unchanged position, F_trial = (I + dt C) F (fluid: J_trial = (1 + dt tr C) J), the model on the
+ * trial state, W (P F^T vol D_inv) (x_i - x_p) ADDED into fOut.  binStart / cellCount / nbr all NULL: particle order (hash query and
+ * global float atomics per node; the gather's sums are formed in the binned kernel's sum-factorised order, not node by node, so that a
+ * particle gets the same trial state and stress on either path); all given (zs_rocm_mpm_bin_particles, zs_rocm_mpm_build_neighbors): one workgroup per grid block,
+ * results do not depend on how fresh the bins are.  The reference's `grid` argument is not read and is left out.
+ * trial: NULL, or float[n][27] = {C_trial:9, F_trial:9 before any plastic projection (fluid: J_trial in slot 0), P F^T vol:9 before
+ * D_inv} written per particle (test hook). */
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_force(zs_rocm_policy *, const zs_rocm_mpm_params *, zs_rocm_particles, const zs_rocm_bht_3 *,
+                                              size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr,
+                                              const float *vIn, float *fOut, float *trial);
+/* ImplicitMPMSystem::multiply (simulation/mpm/ImplicitMPM.hpp:33-59): out := 0, the force operator, then on every entry whose node has
+ * grid mass > 0 out[i] = (out[i] dt dt + m) vIn[i] (ForceDtSqrPlusMass :16-31, element-wise as written). */
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_multiply(zs_rocm_policy *, const zs_rocm_mpm_params *, zs_rocm_particles, const zs_rocm_bht_3 *,
+                                                 const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount,
+                                                 const int *nbr, const float *vIn, float *out);
+/* ImplicitMPMSystem::project (Projector, simulation/mpm/ImplicitMPM.hpp:61-124): collider.resolveCollision(pos, vel) on nodes with
+ * mass > 0, pos = (key * side + cell) * dx as zs_rocm_mpm_apply_boundary forms it; nodes without mass are zeroed.  collider NULL: only
+ * the zeroing. */
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_project(zs_rocm_policy *, const zs_rocm_mpm_params *, const zs_rocm_bht_3 *, const float *grid,
+                                                size_t nblocks, const zs_rocm_collider *collider, float *inout);
+/* ImplicitMPMSystem::precondition (DivPernodeMass, simulation/mpm/ImplicitMPM.hpp:126-152): out = in / m where m > 0 (IEEE division),
+ * other entries untouched */
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_precondition(zs_rocm_policy *, const float *grid, size_t nblocks, int side, const float *in,
+                                                     float *out);
+/* dof-vector operators on n floats (math/linear/LinearOperators.hpp:14-72): DofAssign{a, b} (b := a), DofFill{a, v},
+ * DofCompwiseOp{op}(a, b, c) with op 0 plus, 1 multiplies, 2 minus, 3 divides (-1 for any other op), LinearCombineOp: c = m a + n_ b.
+ * A NULL policy or vector: nothing is touched (-1 from zs_rocm_dof_compwise, a plain return from the void calls). */
+ZS_ROCM_EXPORT void zs_rocm_dof_assign(zs_rocm_policy *, const float *a, float *b, size_t n);
+ZS_ROCM_EXPORT void zs_rocm_dof_fill(zs_rocm_policy *, float *a, float v, size_t n);
+ZS_ROCM_EXPORT int zs_rocm_dof_compwise(zs_rocm_policy *, int op, const float *a, const float *b, float *c, size_t n);
+ZS_ROCM_EXPORT void zs_rocm_dof_linear_combine(zs_rocm_policy *, float m, const float *a, float n_, const float *b, float *c, size_t n);
+/* ConjugateGradient::dotProduct (math/linear/ConjugateGradient.hpp:60-69) without the temporary of products: *out (device) = sum a_i b_i */
+ZS_ROCM_EXPORT void zs_rocm_dof_dot(zs_rocm_policy *, const float *a, const float *b, size_t n, float *out);
+/* ConjugateGradient::solve (math/linear/ConjugateGradient.hpp:72-161) on the system above: A = multiply, projection with `collider`
+ * (may be NULL), preconditioner = division by the node mass.  x: start value in, solution out; *iters (host, may be NULL): iterations
+ * run.  maxIters 0 returns with x unchanged.  The reference's debug prints and its getchar() (:158) are left out. */
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_solve(zs_rocm_policy *, const zs_rocm_mpm_params *, zs_rocm_particles, const zs_rocm_bht_3 *,
+                                              const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount,
+                                              const int *nbr, const zs_rocm_collider *collider, const float *b, float *x, int maxIters,
+                                              float tol, float relTol, int *iters);
 /* ---- slotted particle storage: the motion-robust form of the fused step (zpc_amd/csrc/mpm_slotted.hip).  Storage = bins x K rounds x
  * 64 lanes in ONE TileVector<f32, 64> (slot (bin, r, lane) = element (bin K + r) 64 + lane), cellMask[bin][lane] = occupied rounds of the
  * cell; a particle is always stored under the cell of its base node, and the step keeps it so.  A particle that changes cell is finished

@@ -397,6 +397,24 @@ def _declare_containers(L):
     L.zs_rocm_collider_init.argtypes = [C.POINTER(Collider), i32, i32, C.POINTER(C.c_float), i32]
     L.zs_rocm_mpm_apply_boundary.argtypes = [vp, PP, vp, vp, sz, C.POINTER(Collider)]
     L.zs_rocm_collider_resolve.argtypes = [vp, C.POINTER(Collider), vp, vp, sz, vp]
+    L.zs_rocm_mpm_implicit_force.argtypes = [vp, PP, Particles, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.zs_rocm_mpm_implicit_multiply.argtypes = [vp, PP, Particles, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.zs_rocm_mpm_implicit_project.argtypes = [vp, PP, vp, vp, sz, C.POINTER(Collider), vp]
+    L.zs_rocm_mpm_implicit_precondition.argtypes = [vp, vp, sz, i32, vp, vp]
+    L.zs_rocm_mpm_implicit_solve.argtypes = [vp, PP, Particles, vp, vp, sz, vp, vp, vp, C.POINTER(Collider), vp, vp, i32, f32, f32,
+                                             C.POINTER(C.c_int)]
+    for name in ("force", "multiply", "project", "precondition", "solve"):
+        getattr(L, "zs_rocm_mpm_implicit_" + name).restype = i32
+    L.zs_rocm_dof_assign.argtypes = [vp, vp, vp, sz]
+    L.zs_rocm_dof_assign.restype = None
+    L.zs_rocm_dof_fill.argtypes = [vp, vp, f32, sz]
+    L.zs_rocm_dof_fill.restype = None
+    L.zs_rocm_dof_compwise.argtypes = [vp, i32, vp, vp, vp, sz]
+    L.zs_rocm_dof_compwise.restype = i32
+    L.zs_rocm_dof_linear_combine.argtypes = [vp, f32, vp, f32, vp, vp, sz]
+    L.zs_rocm_dof_linear_combine.restype = None
+    L.zs_rocm_dof_dot.argtypes = [vp, vp, vp, sz, vp]
+    L.zs_rocm_dof_dot.restype = None
     L.zs_rocm_mpm_halo_pack.argtypes = [vp, vp, vp, sz, i32, i32, i32, vp]
     L.zs_rocm_mpm_halo_unpack.argtypes = [vp, vp, vp, sz, i32, i32, i32, vp, i32]
 

@@ -20,12 +20,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # into v_pk_*_f32 (same FLOP rate as two scalar ops on CDNA4) and pays ~25 % extra v_mov to form the register pairs:
 # 901 -> 772 instructions and ~2390 -> ~1540 issue cycles for the SVD alone (MI355X guide, 5.6: "an anti-lever").
 EXTRA_FLAGS = {"mpm_slotted.hip": ["-fno-slp-vectorize"], "mpm_slotblk.hip": ["-fno-slp-vectorize"], "mpm.hip": ["-fno-slp-vectorize"], "mpm_p2g.hip": ["-fno-slp-vectorize"], "mpm_g2p.hip": ["-fno-slp-vectorize"],
-               "mpm_c2.hip": ["-fno-slp-vectorize"],
+               "mpm_c2.hip": ["-fno-slp-vectorize"], "mpm_implicit.hip": ["-fno-slp-vectorize"],
                "mpm_fused.hip": ["-fno-slp-vectorize"], "mpm_fused4.hip": ["-fno-slp-vectorize"], "mpm_fused8.hip": ["-fno-slp-vectorize"],
                # morton codes must round like the reference's scalar code (no fused centre/offset arithmetic)
                "lbvh.hip": ["-ffp-contract=off"],
                # finite-difference normals of the analytic colliders (eps = 1e-6 in float) must round like the reference's
-               "collider.hip": ["-ffp-contract=off"]}
+               "collider.hip": ["-ffp-contract=off"], "mpm_implicit_project.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst):

@@ -476,6 +476,69 @@ class MpmTransfer:
         lib().zs_rocm_mpm_g2p(self.pol.handle, C.byref(self.params), self.particles(), self.table.handle, self.grid.data_ptr(),
                               self.nblocks, bs, cc, nb)
 
+    # ------------------------------------------------------------------ implicit system (G2P2G.hpp, ImplicitMPM.hpp, ConjugateGradient.hpp)
+    def dof_vector(self):
+        """a zeroed dof vector [nblocks * side^3, 3]: entry 3 * (block * side^3 + cell) + d, dof_view<space, 3>(Vector<float>)"""
+        return torch.zeros(self.nblocks * self.side ** 3, 3, dtype=torch.float32, device=self.device)
+
+    def _bins(self, binned):
+        binned = self.binned if binned is None else binned
+        if self.slotted:
+            raise RuntimeError("the implicit operators read compact storage: unslot() first")
+        if binned:
+            return self.bin_start.data_ptr(), self.cell_count.data_ptr(), self.nbr.data_ptr()
+        return None, None, None
+
+    def _check_dof(self, *vs):
+        for v in vs:
+            if v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != self.nblocks * self.side ** 3 * 3:
+                raise ValueError("a dof vector is a contiguous float32 tensor of nblocks * side^3 * 3 entries (dof_vector())")
+
+    def implicit_force(self, v, out, trial=None, binned=None):
+        """G2P2GTransfer: internal grid forces at the trial node velocities v, ADDED into out; no particle attribute changes.
+        trial: optional float32 [n, 27] tensor that receives {C_trial, F_trial (fluid: J_trial), P F^T vol} per particle (test hook)."""
+        self._check_dof(v, out)
+        if trial is not None and (trial.dtype != torch.float32 or not trial.is_contiguous() or trial.numel() != self.n * 27):
+            raise ValueError("trial: contiguous float32 [n, 27]")
+        bs, cc, nb = self._bins(binned)
+        if lib().zs_rocm_mpm_implicit_force(self.pol.handle, C.byref(self.params), self.particles(), self.table.handle, self.nblocks, bs, cc,
+                                            nb, v.data_ptr(), out.data_ptr(), trial.data_ptr() if trial is not None else None) != 0:
+            raise RuntimeError("zs_rocm_mpm_implicit_force refused its arguments")
+
+    def implicit_multiply(self, v, out, binned=None):
+        """ImplicitMPMSystem::multiply: out = (f(v) dt^2 + m) v entry-wise on nodes with mass, 0 elsewhere (m: self.grid channel 0)"""
+        self._check_dof(v, out)
+        bs, cc, nb = self._bins(binned)
+        if lib().zs_rocm_mpm_implicit_multiply(self.pol.handle, C.byref(self.params), self.particles(), self.table.handle,
+                                               self.grid.data_ptr(), self.nblocks, bs, cc, nb, v.data_ptr(), out.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mpm_implicit_multiply refused its arguments")
+
+    def implicit_project(self, collider, inout):
+        """ImplicitMPMSystem::project: resolveCollision on nodes with mass, nodes without mass zeroed; collider None: only the zeroing"""
+        self._check_dof(inout)
+        if lib().zs_rocm_mpm_implicit_project(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(), self.nblocks,
+                                              C.byref(collider) if collider is not None else None, inout.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mpm_implicit_project refused its arguments")
+
+    def implicit_precondition(self, v, out):
+        """ImplicitMPMSystem::precondition: out = v / m on nodes with mass, other entries untouched"""
+        self._check_dof(v, out)
+        if lib().zs_rocm_mpm_implicit_precondition(self.pol.handle, self.grid.data_ptr(), self.nblocks, self.side, v.data_ptr(),
+                                                   out.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mpm_implicit_precondition refused its arguments")
+
+    def implicit_solve(self, b, x, max_iters=1000, tol=1e-6, rel_tol=0.5, collider=None, binned=None):
+        """ConjugateGradient::solve on the implicit system (defaults: ConjugateGradient.hpp:35-37); x is the start value and receives
+        the solution.  Returns the number of iterations."""
+        self._check_dof(b, x)
+        bs, cc, nb = self._bins(binned)
+        it = C.c_int(0)
+        if lib().zs_rocm_mpm_implicit_solve(self.pol.handle, C.byref(self.params), self.particles(), self.table.handle, self.grid.data_ptr(),
+                                            self.nblocks, bs, cc, nb, C.byref(collider) if collider is not None else None, b.data_ptr(),
+                                            x.data_ptr(), int(max_iters), float(tol), float(rel_tol), C.byref(it)) != 0:
+            raise RuntimeError("zs_rocm_mpm_implicit_solve refused its arguments")
+        return it.value
+
     # ------------------------------------------------------------------ gather-style transfers (P2C2G.hpp / G2C2P.hpp)
     def build_buckets(self, displacement=0.0, dense=False):
         """IndexBuckets of cell size dx over the current positions (index_buckets_for_particles, displacement 0): bucket = the cell
