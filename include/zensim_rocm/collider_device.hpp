@@ -4,6 +4,7 @@
 // (simulation/grid/GridOp.hpp:111-164).  Plain struct = zs_rocm_collider of the C ABI; usable inside user lambdas.
 // The arithmetic follows the reference operation by operation (the cuboid / cylinder normals are float finite differences
 // with eps = 1e-6, so evaluation order matters): compile translation units that use it with -ffp-contract=off.
+// resolve_with takes the shape as a parameter: the sparse level-set collider (levelset_device.hpp) runs the same transform and response.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -104,22 +105,39 @@ struct ColliderDev : zs_rocm_collider {
     to_material(x, xmb, X);
     return signed_distance(X) < 0.f;
   }
+  // getMaterialVelocity: the analytic shapes have none (the term is left out of v_object, not added as zeros)
+  __host__ __device__ __forceinline__ bool material_velocity(const float (&)[3], float (&)[3]) const { return false; }
   // Collider::resolveCollision(x, v, erosion) (Collider.h:82-112); returns true when x is inside
   __host__ __device__ __forceinline__ bool resolveCollision(const float (&x)[3], float (&v)[3], float erosion = 0.f) const {
+    return resolve_with(*this, x, v, erosion);
+  }
+  // the same with signed distance, normal and material velocity (all in material space) taken from `shape`: signed_distance(X),
+  // normal(X, n), material_velocity(X, vm) -> false when the shape has none.  Type and motion are this collider's.
+  template <class Shape>
+  __host__ __device__ __forceinline__ bool resolve_with(const Shape &shape, const float (&x)[3], float (&v)[3], float erosion = 0.f) const {
     float xmb[3], X[3];
     to_material(x, xmb, X);
-    if (!(signed_distance(X) < -erosion)) return false;
+    if (!(shape.signed_distance(X) < -erosion)) return false;
     const float one_over_s = 1 / s, k = dsdt * one_over_s;
-    // v_object = omega x (x-b) + (s'/s)(x-b) + R s X' + b'   (X' = material velocity = 0 for the analytic shapes)
+    // v_object = omega x (x-b) + (s'/s)(x-b) + R s X' + b'   (X' = material velocity)
     float vo[3] = {omega[1] * xmb[2] - omega[2] * xmb[1], omega[2] * xmb[0] - omega[0] * xmb[2], omega[0] * xmb[1] - omega[1] * xmb[0]};
+    float vm[3];
+    if (shape.material_velocity(X, vm)) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) vo[d] = (vo[d] + k * xmb[d]) + dbdt[d];
+      for (int d = 0; d < 3; ++d) {
+        const float u = ((R[3 * d] * s) * vm[0] + (R[3 * d + 1] * s) * vm[1]) + (R[3 * d + 2] * s) * vm[2];  // (R s) X'
+        vo[d] = ((vo[d] + k * xmb[d]) + u) + dbdt[d];
+      }
+    } else {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) vo[d] = (vo[d] + k * xmb[d]) + dbdt[d];
+    }
     if (type == ZS_ROCM_COLLIDER_STICKY) {
 #pragma unroll
       for (int d = 0; d < 3; ++d) v[d] = vo[d];
     } else {
       float nm[3], n[3];
-      normal(X, nm);
+      shape.normal(X, nm);
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
         v[d] -= vo[d];

@@ -357,6 +357,44 @@ template <int dim_, class T, int Side> struct SparseGridView {
   template <int N, kernel_e kt = kernel_e::linear> __device__ __forceinline__ packed_t<N> wPack(dim_t<N> t, const char *prop, const coord_type &x, kernel_t<kt> k = {}) const {
     return iPack(t, propertyOffset(prop), worldToIndex(x), k);
   }
+  // the level-set calls (:520-545), dim 3 / float / Side 8 with the properties "sdf" and optionally "v": what Collider{view, type}
+  // below evaluates.  The arithmetic is zsr::LevelSetView's (levelset_device.hpp), so the bits equal the C ABI's level-set entries;
+  // build the translation unit with -ffp-contract=off.
+  ZS_FUNCTION zsr::LevelSetView levelSetView() const {
+    static_assert(dim_ == 3 && Side == 8 && std::is_same_v<T, float>, "level sets are SparseGrid<3, f32, 8>");
+    zsr::LevelSetView l{};
+    l.table.keys = _table.t.keys; l.table.indices = _table.t.indices; l.table.status = _table.t.status; l.table.activeKeys = _table.t.activeKeys;
+    l.table.cnt = _table.t.cnt; l.table.success = _table.t.success;
+    l.table.tableSize = _table.t.tableSize; l.table.numBuckets = _table.t.numBuckets;
+    l.table.hf0x = _table.t.hf[0]; l.table.hf0y = _table.t.hf[1]; l.table.hf1x = _table.t.hf[2]; l.table.hf1y = _table.t.hf[3];
+    l.table.hf2x = _table.t.hf[4]; l.table.hf2y = _table.t.hf[5];
+    l.tiles = _grid._p;
+    l.numBlocks = _grid._n / block_size;
+    l.numChannels = _grid._C;
+    l.sdfChannel = propertyOffset("sdf");
+    l.velChannel = propertyOffset("v");
+    l.h = _dx;
+    for (int d = 0; d < 3; ++d) l.origin[d] = _origin[d];
+    l.background = _background;
+    l.stats = nullptr;
+    return l;
+  }
+  __device__ __forceinline__ T getSignedDistance(const coord_type &x) const {
+    const zsr::LevelSetView l = levelSetView();
+    return l.getSignedDistance(zsr::LevelSetDirectFetch(l), x.v);
+  }
+  __device__ __forceinline__ coord_type getNormal(const coord_type &x) const {
+    const zsr::LevelSetView l = levelSetView();
+    coord_type n;
+    l.getNormal(zsr::LevelSetDirectFetch(l), x.v, n.v);
+    return n;
+  }
+  __device__ __forceinline__ coord_type getMaterialVelocity(const coord_type &x) const {
+    const zsr::LevelSetView l = levelSetView();
+    coord_type vm;
+    l.getMaterialVelocity(zsr::LevelSetDirectFetch(l), x.v, vm.v);
+    return vm;
+  }
   // staggered (MAC) sampling: channel chn + f lives on the faces normal to axis f (:584-609, :657-701)
   template <kernel_e kt = kernel_e::linear> __device__ __forceinline__ T iStaggeredSample(int chn, int f, const coord_type &X, kernel_t<kt> = {}) const {
     return iArena<kt>(X, f).isample(chn + f, _background);
@@ -403,6 +441,38 @@ template <int dim_, class T, int Side> struct SparseGridView {
     return r;
   }
 };
+
+// zs::Collider<LS> (geometry/Collider.h:10-110) over a level-set view: `Collider{view, collider_e::Slip}.resolveCollision(x, v)` inside
+// a kernel.  Identity transform unless the members are set (setTranslation / setRotation of the reference are plain members here).
+enum struct collider_e : int { Sticky = 0, Slip = 1, Separate = 2 };  // geometry/Collider.h:8
+template <class LS> struct Collider {
+  using TV = small_vec<float, 3>;
+  LS levelset;
+  collider_e type = collider_e::Sticky;
+  float s = 1.f, dsdt = 0.f;
+  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};  // row-major
+  float omega[3] = {0.f, 0.f, 0.f}, b[3] = {0.f, 0.f, 0.f}, dbdt[3] = {0.f, 0.f, 0.f};
+  __device__ __forceinline__ zsr::LevelSetColliderDev dev() const {
+    zsr::LevelSetColliderDev c;
+    c.motion.geometry = 0;
+    c.motion.type = (int)type;
+    for (int i = 0; i < 8; ++i) c.motion.param[i] = 0.f;
+    c.motion.s = s;
+    c.motion.dsdt = dsdt;
+    for (int i = 0; i < 9; ++i) c.motion.R[i] = R[i];
+    for (int i = 0; i < 3; ++i) { c.motion.omega[i] = omega[i]; c.motion.b[i] = b[i]; c.motion.dbdt[i] = dbdt[i]; }
+    c.ls = levelset.levelSetView();
+    return c;
+  }
+  __device__ __forceinline__ bool queryInside(const TV &x) const {
+    const zsr::LevelSetColliderDev c = dev();
+    float xmb[3], X[3];
+    c.motion.to_material(x.v, xmb, X);
+    return c.ls.getSignedDistance(zsr::LevelSetDirectFetch(c.ls), X) < 0.f;
+  }
+  __device__ __forceinline__ bool resolveCollision(const TV &x, TV &v, float erosion = 0.f) const { return dev().resolveCollision(x.v, v.v, erosion); }
+};
+template <class LS> Collider(LS, collider_e) -> Collider<LS>;
 
 // SparseGrid<dim, T, Side> (geometry/SparseGrid.hpp:16-188)
 template <int dim_ = 3, class T = float, int Side = 8> struct SparseGrid {

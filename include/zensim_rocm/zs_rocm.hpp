@@ -28,6 +28,7 @@
 
 #include "../zs_rocm.h"
 #include "bht_device.hpp"
+#include "levelset_device.hpp"
 #include "merge_sort.hpp"
 #include "hashtable_device.hpp"
 #include "lbvh_device.hpp"

@@ -689,6 +689,49 @@ ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_solve(zs_rocm_policy *, const zs_rocm_mp
                                               const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount,
                                               const int *nbr, const zs_rocm_collider *collider, const float *b, float *x, int maxIters,
                                               float tol, float relTol, int *iters);
+/* ---- sparse level-set colliders (include/zensim_rocm/levelset_device.hpp, zpc_amd/csrc/levelset.hip): LevelSetBoundary<SparseGrid<3>>, the
+ * first member of GeneralBoundary (geometry/Collider.h:246-252), as the boundary of the two grid passes that take one.
+ * The level set: a SparseGrid<3, f32, 8> -- `table` a bht<int, 3, int, 16> keyed by block ORIGINS (multiples of 8, index space), `tiles`
+ * the data of a TileVector<f32, 512> with numChannels channels and room for numBlocks blocks -- holding "sdf" in channel sdfChannel and,
+ * when velChannel >= 0, "v" in channels velChannel .. velChannel + 2.  index = (world - origin) / h.  Cells of absent blocks read as
+ * `background` (every channel, as the reference's sampling does).  getSignedDistance / getNormal / getMaterialVelocity:
+ * geometry/SparseGrid.hpp:520-545 (linear kernel; normal = central differences at +- h / 4, normalised).
+ * stats: NULL, or 4 device words the block kernels ADD to, one count per grid block and launch: [0] blocks culled (no staged sdf value is
+ * negative: a trilinear field of non-negative values has no interior point), [1] blocks evaluated from the staged footprint, [2] blocks
+ * evaluated by direct hash queries (footprint over the staging budget), [3] unused. */
+typedef struct zs_rocm_levelset {
+  zs_rocm_bht_view_lite table;
+  const float *tiles;
+  size_t numBlocks;
+  int numChannels, sdfChannel, velChannel;
+  float h;
+  float origin[3];
+  float background;
+  unsigned *stats;
+} zs_rocm_levelset;
+/* The int-returning calls below validate their arguments first and return -1 with nothing written (a level set needs table and tiles,
+ * channels inside numChannels, h > 0; a collider used with one needs a type 0..2 and s != 0), else 0. */
+/* bulk sampling at n world-space points x[n][3] (test hook): sdf[n], normal[n][3], vel[n][3]; each output may be NULL */
+ZS_ROCM_EXPORT int zs_rocm_levelset_sample(zs_rocm_policy *, const zs_rocm_levelset *, const float *x, size_t n, float *sdf, float *normal,
+                                           float *vel);
+/* bulk Collider<LevelSet>::resolveCollision (geometry/Collider.h:80-110) on n points, like zs_rocm_collider_resolve: `collider` gives type
+ * and motion (s, dsdt, R, omega, b, dbdt; geometry and param are not read), the level set the signed distance, the normal and the
+ * R s getMaterialVelocity(X) term of v_object.  inside[n] may be NULL. */
+ZS_ROCM_EXPORT int zs_rocm_levelset_collider_resolve(zs_rocm_policy *, const zs_rocm_collider *collider, const zs_rocm_levelset *, const float *x,
+                                                     float *v, size_t n, int *inside);
+/* zs_rocm_mpm_apply_boundary with a level-set collider: one workgroup per grid block stages the block's footprint in the level set into
+ * LDS; every node gets the bits zs_rocm_levelset_collider_resolve gives at (key * side + cell) * dx */
+ZS_ROCM_EXPORT int zs_rocm_mpm_apply_boundary_levelset(zs_rocm_policy *, const zs_rocm_mpm_params *, const zs_rocm_bht_3 *, float *grid,
+                                                       size_t nblocks, const zs_rocm_collider *collider, const zs_rocm_levelset *);
+/* zs_rocm_mpm_implicit_project with a level-set collider; collider and level set both NULL: only the zeroing */
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_project_levelset(zs_rocm_policy *, const zs_rocm_mpm_params *, const zs_rocm_bht_3 *, const float *grid,
+                                                         size_t nblocks, const zs_rocm_collider *collider, const zs_rocm_levelset *,
+                                                         float *inout);
+/* zs_rocm_mpm_implicit_solve projecting with a level-set collider (the same driver; collider and level set both NULL: no collider) */
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_solve_levelset(zs_rocm_policy *, const zs_rocm_mpm_params *, zs_rocm_particles, const zs_rocm_bht_3 *,
+                                                       const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount,
+                                                       const int *nbr, const zs_rocm_collider *collider, const zs_rocm_levelset *,
+                                                       const float *b, float *x, int maxIters, float tol, float relTol, int *iters);
 /* ---- slotted particle storage: the motion-robust form of the fused step (zpc_amd/csrc/mpm_slotted.hip).  Storage = bins x K rounds x
  * 64 lanes in ONE TileVector<f32, 64> (slot (bin, r, lane) = element (bin K + r) 64 + lane), cellMask[bin][lane] = occupied rounds of the
  * cell; a particle is always stored under the cell of its base node, and the step keeps it so.  A particle that changes cell is finished
@@ -921,6 +964,8 @@ typedef struct zs_rocm_mpm_step {
                                             exchange buffer (zs_rocm_mpm_halo_pack, chn0 = 0, nchn = 1) on commPolicy's stream at the moment the exchange starts.  Only the
                                             boundary blocks write those nodes, so it must equal the same pack taken after the step: the check that the hand-over of a
                                             schedule lets the exchange see complete sums (tests/test_dist_gpu.py) */
+  const zs_rocm_levelset *levelset;      /* NULL, or the boundary is this level set with `collider`'s type and motion (zs_rocm_mpm_apply_boundary_levelset);
+                                            a level set without a collider is refused (-1) before anything runs */
 } zs_rocm_mpm_step;
 #define ZS_ROCM_STEP_EVENTS 8
 #define ZS_ROCM_RANGES_IN_TURN 0

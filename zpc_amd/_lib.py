@@ -70,7 +70,8 @@ class MpmStep(C.Structure):
                 ("nblocks", C.c_size_t), ("storage", C.c_void_p), ("writeAll", C.c_int), ("extf", C.c_float * 3),
                 ("maxVelSqr", C.c_void_p), ("collider", C.c_void_p), ("nBoundary", C.c_size_t), ("dist", C.c_void_p),
                 ("plan", C.c_void_p), ("commPolicy", C.c_void_p), ("haloGrid", C.c_void_p), ("evTransferBegin", C.c_void_p),
-                ("evTransferEnd", C.c_void_p), ("evBreakdown", C.POINTER(C.c_void_p)), ("haloChannels", C.c_int), ("rangeSchedule", C.c_int), ("handoverSnapshot", C.c_void_p)]
+                ("evTransferEnd", C.c_void_p), ("evBreakdown", C.POINTER(C.c_void_p)), ("haloChannels", C.c_int), ("rangeSchedule", C.c_int), ("handoverSnapshot", C.c_void_p),
+                ("levelset", C.c_void_p)]
 
 
 class MpmParams(C.Structure):
@@ -105,6 +106,13 @@ class Collider(C.Structure):
     """zs_rocm_collider (include/zs_rocm.h): Collider<AnalyticLevelSet<...>, f32, 3> of geometry/Collider.h"""
     _fields_ = [("geometry", C.c_int), ("type", C.c_int), ("param", C.c_float * 8), ("s", C.c_float), ("dsdt", C.c_float),
                 ("R", C.c_float * 9), ("omega", C.c_float * 3), ("b", C.c_float * 3), ("dbdt", C.c_float * 3)]
+
+
+class LevelSet(C.Structure):
+    """zs_rocm_levelset (include/zs_rocm.h): LevelSetBoundary<SparseGrid<3, f32, 8>> as a POD of device pointers and scalars"""
+    _fields_ = [("table", BhtViewLite), ("tiles", C.c_void_p), ("numBlocks", C.c_size_t), ("numChannels", C.c_int),
+                ("sdfChannel", C.c_int), ("velChannel", C.c_int), ("h", C.c_float), ("origin", C.c_float * 3), ("background", C.c_float),
+                ("stats", C.c_void_p)]
 
 
 def _declare(L):
@@ -405,6 +413,16 @@ def _declare_containers(L):
                                              C.POINTER(C.c_int)]
     for name in ("force", "multiply", "project", "precondition", "solve"):
         getattr(L, "zs_rocm_mpm_implicit_" + name).restype = i32
+    PC, PL = C.POINTER(Collider), C.POINTER(LevelSet)
+    L.zs_rocm_levelset_sample.argtypes = [vp, PL, vp, sz, vp, vp, vp]
+    L.zs_rocm_levelset_collider_resolve.argtypes = [vp, PC, PL, vp, vp, sz, vp]
+    L.zs_rocm_mpm_apply_boundary_levelset.argtypes = [vp, PP, vp, vp, sz, PC, PL]
+    L.zs_rocm_mpm_implicit_project_levelset.argtypes = [vp, PP, vp, vp, sz, PC, PL, vp]
+    L.zs_rocm_mpm_implicit_solve_levelset.argtypes = [vp, PP, Particles, vp, vp, sz, vp, vp, vp, PC, PL, vp, vp, i32, f32, f32,
+                                                      C.POINTER(C.c_int)]
+    for name in ("levelset_sample", "levelset_collider_resolve", "mpm_apply_boundary_levelset", "mpm_implicit_project_levelset",
+                 "mpm_implicit_solve_levelset"):
+        getattr(L, "zs_rocm_" + name).restype = i32
     L.zs_rocm_dof_assign.argtypes = [vp, vp, vp, sz]
     L.zs_rocm_dof_assign.restype = None
     L.zs_rocm_dof_fill.argtypes = [vp, vp, f32, sz]

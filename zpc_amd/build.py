@@ -25,7 +25,9 @@ EXTRA_FLAGS = {"mpm_slotted.hip": ["-fno-slp-vectorize"], "mpm_slotblk.hip": ["-
                # morton codes must round like the reference's scalar code (no fused centre/offset arithmetic)
                "lbvh.hip": ["-ffp-contract=off"],
                # finite-difference normals of the analytic colliders (eps = 1e-6 in float) must round like the reference's
-               "collider.hip": ["-ffp-contract=off"], "mpm_implicit_project.hip": ["-ffp-contract=off"]}
+               "collider.hip": ["-ffp-contract=off"], "mpm_implicit_project.hip": ["-ffp-contract=off"],
+               # the level-set normal is a float central difference at +- h / 4 (include/zensim_rocm/levelset_device.hpp)
+               "levelset.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst):
@@ -37,7 +39,9 @@ def build_hip(force=False, verbose=True):
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "zs_rocm.h")]
+    face = os.path.join(ROOT, "include", "zensim_rocm")
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "zs_rocm.h")] \
+        + [os.path.join(face, f) for f in os.listdir(face) if f.endswith("_device.hpp")]
     objs, procs = [], []
     for s in srcs:
         src = os.path.join(CSRC, s)
@@ -91,6 +95,22 @@ def build_ofb_test(verbose=True):
     return out
 
 
+def build_levelset_test(verbose=True):
+    """tests/cpp/test_levelset.hip: Collider{sparseGridView, type}.resolveCollision in a user lambda against the C ABI's level-set
+    entries; built without FP contraction like every translation unit that evaluates a level set."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_levelset.hip")
+    out = os.path.join(LIBDIR, "test_levelset")
+    face = os.path.join(ROOT, "include", "zensim_rocm")
+    deps = [src, LIB] + [os.path.join(face, f) for f in os.listdir(face) if f.endswith(".hpp")]
+    if os.path.exists(src) and any(_newer(d, out) for d in deps):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), src,
+               "-L", LIBDIR, "-lzsrocm", "-Wl,-rpath,$ORIGIN", "-o", out]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return out
+
+
 def build_oracle(verbose=True):
     """CPU restatement (always) and, where /root/reference exists, the in-place build of the reference's
     header-only numerics (oracle/_ref).  Building the checker is not using it."""
@@ -105,4 +125,5 @@ if __name__ == "__main__":
     print(build_hip(force=force))
     build_cpp_face_test()
     build_ofb_test()
+    build_levelset_test()
     build_oracle()

@@ -146,6 +146,11 @@ inline unsigned ceil_div(size_t a, size_t b) { return (unsigned)((a + b - 1) / b
 int mpm_g2p2g_slots_signal(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab, const float *gridA,
                            float *gridB, size_t nblocks, const zs_rocm_slot_storage *st, int writeAll, size_t blockBegin, size_t blockEnd, int finish,
                            unsigned long long *signal, size_t signalBlocks);
+// levelset.hip: the checks of a (collider, level set) pair, and the block kernels on a stream (dof == nullptr: boundary pass on `grid`;
+// else the projection of `dof`, grid only read); used by mpm_implicit.hip and dist.hip
+bool levelset_collider_ok(const zs_rocm_collider *collider, const zs_rocm_levelset *levelset);
+void levelset_blocks_enqueue(hipStream_t stream, const zs_rocm_mpm_params *p, const int *activeKeys, float *grid, size_t nblocks,
+                             const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, float *dof);
 
 }  // namespace zsr
 

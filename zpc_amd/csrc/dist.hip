@@ -427,6 +427,7 @@ extern "C" {
 // the schedule itself has no counterpart (zpc has no collective layer).  Returns 0, -1 on bad arguments or an RCCL error.
 int zs_rocm_mpm_step_slotted(zs_rocm_policy *pol, const zs_rocm_mpm_step *a) {
   if (!pol || !a || !a->params || !a->table || !a->gridA || !a->gridB || !a->storage) return -1;
+  if (a->levelset && !zsr::levelset_collider_ok(a->collider, a->levelset)) return -1;
   const size_t nb = a->nblocks;
   if (!nb) return 0;
   const int side = a->params->side;
@@ -564,7 +565,8 @@ int zs_rocm_mpm_step_slotted(zs_rocm_policy *pol, const zs_rocm_mpm_step *a) {
   }
   if (a->maxVelSqr) zs_rocm_memset(pol, a->maxVelSqr, 0, sizeof(float));
   zs_rocm_mpm_grid_update(pol, a->params, a->gridB, nb, a->extf, a->maxVelSqr);
-  if (a->collider) zs_rocm_mpm_apply_boundary(pol, a->params, a->table, a->gridB, nb, a->collider);
+  if (a->levelset) rc = zs_rocm_mpm_apply_boundary_levelset(pol, a->params, a->table, a->gridB, nb, a->collider, a->levelset);
+  else if (a->collider) zs_rocm_mpm_apply_boundary(pol, a->params, a->table, a->gridB, nb, a->collider);
   bd(6, pol);
   if (a->dist && a->maxVelSqr) rc = zs_rocm_dist_allreduce_f32(a->dist, pol, a->maxVelSqr, 1, 1);
   bd(7, pol);

@@ -186,8 +186,15 @@ static void implicit_precondition(Launch &L, const float *grid, size_t nblocks, 
   if (side == 4) hipLaunchKernelGGL((implicit_precondition_kernel<4>), dim3(ceil_div(ne, 256)), dim3(256), 0, L.stream, grid, in, out, ne);
   else hipLaunchKernelGGL((implicit_precondition_kernel<8>), dim3(ceil_div(ne, 256)), dim3(256), 0, L.stream, grid, in, out, ne);
 }
-static void implicit_project(Launch &L, const ImplicitArgs &a, const zs_rocm_collider *collider, float *inout) {
-  implicit_project_enqueue(L.stream, a.p, (const int *)a.tab->t.dev().activeKeys, a.grid, a.nblocks, collider, inout);
+// levelset set: `collider` gives type and motion, the level set the shape (the grid is only read there too)
+static void implicit_project(Launch &L, const ImplicitArgs &a, const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, float *inout) {
+  const int *keys = (const int *)a.tab->t.dev().activeKeys;
+  if (levelset) levelset_blocks_enqueue(L.stream, a.p, keys, const_cast<float *>(a.grid), a.nblocks, collider, levelset, inout);
+  else implicit_project_enqueue(L.stream, a.p, keys, a.grid, a.nblocks, collider, inout);
+}
+// a level set comes with a collider (type and motion); neither: no boundary
+static bool boundary_ok(const zs_rocm_collider *collider, const zs_rocm_levelset *levelset) {
+  return levelset ? levelset_collider_ok(collider, levelset) : true;
 }
 
 }  // namespace zsr
@@ -217,13 +224,23 @@ int zs_rocm_mpm_implicit_multiply(zs_rocm_policy *pol, const zs_rocm_mpm_params 
   return 0;
 }
 
-int zs_rocm_mpm_implicit_project(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, const zs_rocm_bht_3 *tab, const float *grid, size_t nblocks,
-                                 const zs_rocm_collider *collider, float *inout) {
+static int implicit_project_entry(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, const zs_rocm_bht_3 *tab, const float *grid, size_t nblocks,
+                                  const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, float *inout) {
   if (!pol || !p || !tab || !grid || !inout || (p->side != 4 && p->side != 8) || !(p->dx > 0.f)) return -1;
+  if (!boundary_ok(collider, levelset) || nblocks > (size_t)0x7fffffff) return -1;
   Launch L(pol, "ImplicitMPMSystem::project");
   const ImplicitArgs a{p, zs_rocm_particles{}, tab, grid, nblocks, nullptr, nullptr, nullptr};
-  implicit_project(L, a, collider, inout);
+  implicit_project(L, a, collider, levelset, inout);
   return 0;
+}
+int zs_rocm_mpm_implicit_project(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, const zs_rocm_bht_3 *tab, const float *grid, size_t nblocks,
+                                 const zs_rocm_collider *collider, float *inout) {
+  return implicit_project_entry(pol, p, tab, grid, nblocks, collider, nullptr, inout);
+}
+int zs_rocm_mpm_implicit_project_levelset(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, const zs_rocm_bht_3 *tab, const float *grid,
+                                          size_t nblocks, const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, float *inout) {
+  if (!levelset && collider) return -1;  // (a collider alone is zs_rocm_mpm_implicit_project's)
+  return implicit_project_entry(pol, p, tab, grid, nblocks, collider, levelset, inout);
 }
 
 int zs_rocm_mpm_implicit_precondition(zs_rocm_policy *pol, const float *grid, size_t nblocks, int side, const float *in, float *out) {
@@ -262,11 +279,13 @@ void zs_rocm_dof_dot(zs_rocm_policy *pol, const float *a, const float *b, size_t
   dof_dot(L, a, b, n, partials, out);
 }
 
-int zs_rocm_mpm_implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab,
-                               const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr,
-                               const zs_rocm_collider *collider, const float *b, float *x, int maxIters, float tol, float relTol, int *iters) {
+// the CG driver of both solve entries
+static int implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab, const float *grid,
+                          size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr, const zs_rocm_collider *collider,
+                          const zs_rocm_levelset *levelset, const float *b, float *x, int maxIters, float tol, float relTol, int *iters) {
   const ImplicitArgs a{p, ps, tab, grid, nblocks, binStart, cellCount, nbr};
   if (!pol || !implicit_args_ok(a, true) || !b || !x || b == x || maxIters < 0) return -1;
+  if (!boundary_ok(collider, levelset) || nblocks > (size_t)0x7fffffff) return -1;
   if (iters) *iters = 0;
   const size_t ne = a.entries();
   if (!ne || maxIters == 0) return 0;  // the reference's loop does not run either and x = xinout comes back as it went in
@@ -279,7 +298,7 @@ int zs_rocm_mpm_implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p,
   // (the reference copies xinout into a member x_ first and back at the end, :77,160: x is updated in place here)
   implicit_multiply(L, a, x, temp, stale);
   dof_compwise(L, DOF_MINUS, b, temp, r, ne);  // r = b - A x
-  implicit_project(L, a, collider, r);
+  implicit_project(L, a, collider, levelset, r);
   dof_assign(L, r, q, ne);                     // (entries without mass: q keeps r there, which the projection has zeroed)
   implicit_precondition(L, grid, nblocks, p->side, r, q);
   dof_assign(L, q, pv, ne);
@@ -291,7 +310,7 @@ int zs_rocm_mpm_implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p,
   for (; iter != maxIters; ++iter) {
     if (resNorm <= localTol) break;
     implicit_multiply(L, a, pv, temp, stale);
-    implicit_project(L, a, collider, temp);
+    implicit_project(L, a, collider, levelset, temp);
     dof_dot(L, temp, pv, ne, partials, scalar);
     const float alpha = zTrk / read_back(L, scalar);
     dof_linear_combine(L, alpha, pv, 1.f, x, x, ne);      // x = x + alpha p
@@ -306,6 +325,18 @@ int zs_rocm_mpm_implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p,
   }
   if (iters) *iters = iter;
   return 0;
+}
+int zs_rocm_mpm_implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab,
+                               const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr,
+                               const zs_rocm_collider *collider, const float *b, float *x, int maxIters, float tol, float relTol, int *iters) {
+  return implicit_solve(pol, p, ps, tab, grid, nblocks, binStart, cellCount, nbr, collider, nullptr, b, x, maxIters, tol, relTol, iters);
+}
+int zs_rocm_mpm_implicit_solve_levelset(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab,
+                                        const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr,
+                                        const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, const float *b, float *x,
+                                        int maxIters, float tol, float relTol, int *iters) {
+  if (!levelset && collider) return -1;  // (a collider alone is zs_rocm_mpm_implicit_solve's)
+  return implicit_solve(pol, p, ps, tab, grid, nblocks, binStart, cellCount, nbr, collider, levelset, b, x, maxIters, tol, relTol, iters);
 }
 
 }  // extern "C"

@@ -1,0 +1,138 @@
+"""Sparse level sets: zs::LevelSetBoundary<SparseGrid<3, f32, 8>> (geometry/Collider.h:246-252, geometry/SparseGrid.hpp) built from a
+dense signed-distance array -- a bht<int, 3, int, 16> keyed by block origins next to a TileVector<f32, 512> with the properties "sdf"
+(1 channel) and optionally "v" (3 channels) -- for MpmTransfer.apply_boundary / implicit_project / implicit_solve / step_slotted
+(levelset=).  Set-up code: numpy and torch for the plumbing, the library's containers for the storage."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import lib, LevelSet
+from .containers import Bht, TileVector
+
+SIDE, BLOCK = 8, 512   # SparseGrid<3, f32, 8>
+
+
+def select_blocks(sdf, band, background, vel=None):
+    """Host part of from_dense (no device needed): the 8^3 blocks of the dense array `sdf` [nx, ny, nz] (cell (i, j, k) = level-set
+    index (i, j, k); the array is padded with `background` up to multiples of 8) that hold a cell with |sdf| < band.
+    Returns (keys [nb, 3] int32 block origins in lexicographic order, cells [nb * 512, C] float32 with C = 1 or 4: sdf, v)."""
+    sdf = np.asarray(sdf, np.float32)
+    if sdf.ndim != 3:
+        raise ValueError("sdf: a dense [nx, ny, nz] array")
+    chans = [sdf]
+    if vel is not None:
+        vel = np.asarray(vel, np.float32)
+        if vel.shape != sdf.shape + (3,):
+            raise ValueError("vel: [nx, ny, nz, 3]")
+        chans += [vel[..., d] for d in range(3)]
+    nb3 = [(n + SIDE - 1) // SIDE for n in sdf.shape]
+    padded = np.full([len(chans)] + [n * SIDE for n in nb3], np.float32(background), np.float32)
+    for c, a in enumerate(chans):
+        padded[c, :sdf.shape[0], :sdf.shape[1], :sdf.shape[2]] = a
+    # [C, bx, 8, by, 8, bz, 8] -> [bx, by, bz, 8, 8, 8, C]: cell offset (x * 8 + y) * 8 + z inside a block, first axis slowest
+    tiles = padded.reshape(len(chans), nb3[0], SIDE, nb3[1], SIDE, nb3[2], SIDE).transpose(1, 3, 5, 2, 4, 6, 0)
+    active = (np.abs(tiles[..., 0]) < np.float32(band)).any(axis=(3, 4, 5))
+    idx = np.argwhere(active)
+    keys = (idx * SIDE).astype(np.int32)
+    cells = np.ascontiguousarray(tiles[active]).reshape(-1, len(chans))
+    return keys, cells
+
+
+class SparseLevelSet:
+    """A level set on the device.  index = (world - origin) / voxel; cells of blocks that are not stored read as `background`."""
+
+    def __init__(self, pol, keys, cells, origin, voxel, background):
+        import torch
+        self.pol = pol
+        self.keys = np.ascontiguousarray(keys, np.int32)
+        nb = self.keys.shape[0]
+        nch = cells.shape[1]
+        if nch not in (1, 4):
+            raise ValueError("cells: [nb * 512, 1] (sdf) or [nb * 512, 4] (sdf, v)")
+        self.has_velocity = nch == 4
+        self.nblocks = nb
+        self.origin = tuple(float(v) for v in origin)
+        self.voxel, self.background = float(voxel), float(background)
+        self.table = Bht(3, max(nb, 1), bucket=16)
+        tags = [("sdf", 1)] + ([("v", 3)] if self.has_velocity else [])
+        self.tiles = TileVector("float", BLOCK, tags, max(nb, 1) * BLOCK)
+        if nb:
+            dk = torch.from_numpy(self.keys).cuda()
+            self.table.assign(pol, dk.data_ptr(), nb)   # block number = position in `keys`
+            dc = torch.from_numpy(np.ascontiguousarray(cells, np.float32)).cuda()
+            lib().zs_rocm_tv_from_aos_f32(pol.handle, dc.data_ptr(), nb * BLOCK, nch, BLOCK, self.tiles.data())
+            pol.syncCtx()
+        self.stats = None
+        self._make_view()
+
+    def _make_view(self):
+        v = LevelSet()
+        v.table = self.table.view()
+        v.tiles = self.tiles.data()
+        v.numBlocks = self.nblocks
+        v.numChannels = self.tiles.numChannels()
+        v.sdfChannel = self.tiles.getPropertyOffset("sdf")
+        v.velChannel = self.tiles.getPropertyOffset("v") if self.has_velocity else -1
+        v.h = self.voxel
+        v.origin = (C.c_float * 3)(*self.origin)
+        v.background = self.background
+        v.stats = self.stats.data_ptr() if self.stats is not None else None
+        self.view = v
+
+    @classmethod
+    def from_dense(cls, pol, sdf, origin, voxel, band, vel=None, background=None):
+        """sdf: dense numpy / torch array [nx, ny, nz], cell (0, 0, 0) at world `origin`, spacing `voxel`; every 8^3 block holding a
+        cell with |sdf| < band is stored.  vel: optional [nx, ny, nz, 3] material velocity.  background defaults to band."""
+        to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        background = band if background is None else background
+        keys, cells = select_blocks(to_np(sdf), band, background, None if vel is None else to_np(vel))
+        return cls(pol, keys, cells, origin, voxel, background)
+
+    @classmethod
+    def from_function(cls, pol, fn, lo, hi, voxel, band, vel_fn=None, background=None):
+        """fn(x [..., 3] float64 world positions) -> signed distance, sampled on the lattice lo + voxel * (i, j, k) that covers [lo, hi]"""
+        lo = np.asarray(lo, np.float64)
+        n = [int(np.ceil((h - l) / voxel)) + 1 for l, h in zip(lo, hi)]
+        x = lo + voxel * np.stack(np.meshgrid(*[np.arange(k) for k in n], indexing="ij"), axis=-1)
+        return cls.from_dense(pol, fn(x), lo, voxel, band, vel=None if vel_fn is None else vel_fn(x), background=background)
+
+    def enable_stats(self):
+        """count, per block-kernel launch and grid block, how the block was handled: stats()[0] culled, [1] staged, [2] direct"""
+        import torch
+        self.stats = torch.zeros(4, dtype=torch.int32, device="cuda")
+        self._make_view()
+
+    def read_stats(self, reset=True):
+        self.pol.syncCtx()
+        s = self.stats.cpu().numpy().astype(np.int64)
+        if reset:
+            self.stats.zero_()
+        return s
+
+    def to_dense(self, lo, hi):
+        """the cells of the index-space box [lo, hi) as a dense array [.., .., .., C] (C = 1 or 4), background where no block is stored;
+        read back from the device: block numbers through the table, values from the tiles"""
+        import torch
+        lo, hi = np.asarray(lo, np.int64), np.asarray(hi, np.int64)
+        nch = 4 if self.has_velocity else 1
+        out = np.full(tuple(hi - lo) + (nch,), np.float32(self.background), np.float32)
+        if not self.nblocks:
+            return out
+        aos = torch.empty(self.nblocks * BLOCK, nch, dtype=torch.float32, device="cuda")
+        lib().zs_rocm_tv_to_aos_f32(self.pol.handle, self.tiles.data(), self.nblocks * BLOCK, nch, BLOCK, aos.data_ptr())
+        blo, bhi = lo // SIDE, (hi + SIDE - 1) // SIDE
+        bk = np.stack(np.meshgrid(*[np.arange(a, b) for a, b in zip(blo, bhi)], indexing="ij"), axis=-1).reshape(-1, 3)
+        q = torch.from_numpy(np.ascontiguousarray(bk * SIDE, np.int32)).cuda()
+        bno = torch.empty(q.shape[0], dtype=torch.int32, device="cuda")
+        self.table.query(self.pol, q.data_ptr(), q.shape[0], bno.data_ptr())
+        self.pol.syncCtx()
+        tiles = aos.cpu().numpy().reshape(self.nblocks, SIDE, SIDE, SIDE, nch)
+        for k, b in zip(bk, bno.cpu().numpy()):
+            if b < 0:
+                continue
+            o = k * SIDE
+            a, e = np.maximum(o, lo), np.minimum(o + SIDE, hi)
+            if (a < e).all():
+                out[a[0] - lo[0]:e[0] - lo[0], a[1] - lo[1]:e[1] - lo[1], a[2] - lo[2]:e[2] - lo[2]] = \
+                    tiles[b, a[0] - o[0]:e[0] - o[0], a[1] - o[1]:e[1] - o[1], a[2] - o[2]:e[2] - o[2]]
+        return out

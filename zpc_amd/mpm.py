@@ -462,9 +462,15 @@ class MpmTransfer:
         lib().zs_rocm_mpm_grid_update(self.pol.handle, C.byref(self.params), self.grid.data_ptr(), self.nblocks, e,
                                       max_vel.data_ptr() if max_vel is not None else None)
 
-    def apply_boundary(self, collider):
+    def apply_boundary(self, collider, levelset=None):
         """ApplyBoundaryConditionOnGridBlocks (simulation/grid/GridOp.hpp:111-164): collider.resolveCollision on every grid node
-        with mass; call after grid_update.  `collider`: make_collider(...)."""
+        with mass; call after grid_update.  `collider`: make_collider(...); with levelset= (a SparseLevelSet or its .view):
+        make_levelset_collider(...), the level set is the shape."""
+        if levelset is not None:
+            if lib().zs_rocm_mpm_apply_boundary_levelset(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(),
+                                                         self.nblocks, C.byref(collider), C.byref(_levelset_view(levelset))) != 0:
+                raise RuntimeError("zs_rocm_mpm_apply_boundary_levelset refused its arguments")
+            return
         lib().zs_rocm_mpm_apply_boundary(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(), self.nblocks,
                                          C.byref(collider))
 
@@ -513,9 +519,16 @@ class MpmTransfer:
                                                self.grid.data_ptr(), self.nblocks, bs, cc, nb, v.data_ptr(), out.data_ptr()) != 0:
             raise RuntimeError("zs_rocm_mpm_implicit_multiply refused its arguments")
 
-    def implicit_project(self, collider, inout):
-        """ImplicitMPMSystem::project: resolveCollision on nodes with mass, nodes without mass zeroed; collider None: only the zeroing"""
+    def implicit_project(self, collider, inout, levelset=None):
+        """ImplicitMPMSystem::project: resolveCollision on nodes with mass, nodes without mass zeroed; collider None: only the zeroing.
+        levelset=: the collider (make_levelset_collider) takes its shape from that level set."""
         self._check_dof(inout)
+        if levelset is not None:
+            if lib().zs_rocm_mpm_implicit_project_levelset(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(),
+                                                           self.nblocks, C.byref(collider) if collider is not None else None,
+                                                           C.byref(_levelset_view(levelset)), inout.data_ptr()) != 0:
+                raise RuntimeError("zs_rocm_mpm_implicit_project_levelset refused its arguments")
+            return
         if lib().zs_rocm_mpm_implicit_project(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(), self.nblocks,
                                               C.byref(collider) if collider is not None else None, inout.data_ptr()) != 0:
             raise RuntimeError("zs_rocm_mpm_implicit_project refused its arguments")
@@ -527,12 +540,19 @@ class MpmTransfer:
                                                    out.data_ptr()) != 0:
             raise RuntimeError("zs_rocm_mpm_implicit_precondition refused its arguments")
 
-    def implicit_solve(self, b, x, max_iters=1000, tol=1e-6, rel_tol=0.5, collider=None, binned=None):
+    def implicit_solve(self, b, x, max_iters=1000, tol=1e-6, rel_tol=0.5, collider=None, binned=None, levelset=None):
         """ConjugateGradient::solve on the implicit system (defaults: ConjugateGradient.hpp:35-37); x is the start value and receives
-        the solution.  Returns the number of iterations."""
+        the solution.  Returns the number of iterations.  levelset=: the projection's collider takes its shape from that level set."""
         self._check_dof(b, x)
         bs, cc, nb = self._bins(binned)
         it = C.c_int(0)
+        if levelset is not None:
+            if lib().zs_rocm_mpm_implicit_solve_levelset(self.pol.handle, C.byref(self.params), self.particles(), self.table.handle,
+                                                         self.grid.data_ptr(), self.nblocks, bs, cc, nb,
+                                                         C.byref(collider) if collider is not None else None, C.byref(_levelset_view(levelset)),
+                                                         b.data_ptr(), x.data_ptr(), int(max_iters), float(tol), float(rel_tol), C.byref(it)) != 0:
+                raise RuntimeError("zs_rocm_mpm_implicit_solve_levelset refused its arguments")
+            return it.value
         if lib().zs_rocm_mpm_implicit_solve(self.pol.handle, C.byref(self.params), self.particles(), self.table.handle, self.grid.data_ptr(),
                                             self.nblocks, bs, cc, nb, C.byref(collider) if collider is not None else None, b.data_ptr(),
                                             x.data_ptr(), int(max_iters), float(tol), float(rel_tol), C.byref(it)) != 0:
@@ -646,11 +666,13 @@ class MpmTransfer:
                 between()
 
     def step_slotted(self, extf=(0.0, 0.0, 0.0), max_vel=None, write_all=False, n_boundary=0, comm=None, plan=None, comm_pol=None,
-                     collider=None, halo_grid=None, events=None, breakdown=None, halo_channels=7, range_schedule=0, handover_snapshot=None):
+                     collider=None, halo_grid=None, events=None, breakdown=None, halo_channels=7, range_schedule=0, handover_snapshot=None,
+                     levelset=None):
         """One whole sub-step on slotted storage behind ONE C-ABI call (zs_rocm_mpm_step_slotted): second grid := 0, fused G2P2G over the
         boundary blocks [0, n_boundary) then the interior, ghost-block exchange of `plan` on comm_pol's stream overlapping the interior,
         grid update (+ collider), CFL allreduce(max) of max_vel.  The grids swap: self.grid is the new one afterwards.
-        comm: NativeComm, plan: NativeHaloPlan (both None on a single rank)."""
+        comm: NativeComm, plan: NativeHaloPlan (both None on a single rank).  levelset=: the boundary is that level set with `collider`'s
+        (make_levelset_collider) type and motion."""
         assert self.slotted
         if getattr(self, "grid2", None) is None or self.grid2.numel() != self.grid.numel():
             self.grid2 = torch.empty_like(self.grid)
@@ -668,6 +690,8 @@ class MpmTransfer:
         a.extf = (C.c_float * 3)(*extf)
         a.maxVelSqr = max_vel.data_ptr() if max_vel is not None else None
         a.collider = C.addressof(collider) if collider is not None else None
+        self._step_levelset = _levelset_view(levelset) if levelset is not None else None   # (kept alive for the call)
+        a.levelset = C.addressof(self._step_levelset) if levelset is not None else None
         a.nBoundary = int(n_boundary)
         a.dist = comm._h if comm is not None else None
         a.plan = plan._h if plan is not None else None
@@ -844,3 +868,15 @@ def make_collider(geometry, ctype, param, s=1.0, dsdt=0.0, R=None, omega=(0, 0, 
     c.b = (C.c_float * 3)(*[float(v) for v in b])
     c.dbdt = (C.c_float * 3)(*[float(v) for v in dbdt])
     return c
+
+
+def make_levelset_collider(ctype, s=1.0, dsdt=0.0, R=None, omega=(0, 0, 0), b=(0, 0, 0), dbdt=(0, 0, 0)):
+    """zs::Collider<LevelSetBoundary<SparseGrid<3>>>{levelset, ctype} with setTranslation / setRotation / scale: type and motion of the
+    collider a level set (zpc_amd.levelset.SparseLevelSet, passed as levelset=) gives the shape to.  The defaults are the identity
+    transform the reference's two call sites build (GridOp.hpp:128-134, ImplicitMPM.hpp:110-114)."""
+    return make_collider(PLANE, ctype, (), s=s, dsdt=dsdt, R=R, omega=omega, b=b, dbdt=dbdt)   # (geometry / param are not read)
+
+
+def _levelset_view(levelset):
+    """the ctypes zs_rocm_levelset of a SparseLevelSet (or the struct itself)"""
+    return levelset.view if hasattr(levelset, "view") else levelset
