@@ -32,6 +32,7 @@
 #include "merge_sort.hpp"
 #include "hashtable_device.hpp"
 #include "lbvh_device.hpp"
+#include "mesh_device.hpp"
 
 #define ZS_LAMBDA __device__
 #define ZS_FUNCTION __forceinline__ __host__ __device__
@@ -711,6 +712,45 @@ struct LBvh {
   zs_rocm_lbvh *_h;
 };
 
+// A triangle mesh as a collider shape (zs_rocm_mesh_*): LBvh over the triangle boxes + pseudonormals.  Inside kernels the view gives
+// closest_point(p[, cap]) -- LBvhView::find_nearest with the point-triangle distance as the functor -- and signed_distance(p[, cap]), with
+// the bits of the bulk entries zs_rocm_mesh_closest_point / zs_rocm_mesh_signed_distance (build with -ffp-contract=off).
+struct TriMeshView : zsr::TriMeshDev {
+  using V3 = small_vec<float, 3>;
+  __device__ __forceinline__ zsr::MeshClosest closest_point(const V3 &p, float cap = 3.402823466e+38f) const { return zsr::TriMeshDev::closest_point(p.v, cap); }
+  __device__ __forceinline__ float signed_distance(const V3 &p, float cap = 3.402823466e+38f) const { return zsr::TriMeshDev::signed_distance(p.v, cap); }
+  __device__ __forceinline__ V3 velocity(const zsr::MeshClosest &m) const {
+    V3 r;
+    zsr::TriMeshDev::velocity_of(m, r.v);
+    return r;
+  }
+};
+struct TriMesh {
+  template <class Pol> TriMesh(const Pol &pol, const Vector<float> &verts, const Vector<int> &tris, const Vector<float> *vel = nullptr)
+      : _h(zs_rocm_mesh_create(pol.handle(), verts.data(), verts.size() / 3, tris.data(), tris.size() / 3, vel ? vel->data() : nullptr)) {
+    if (!_h) throw std::runtime_error("TriMesh: invalid arguments");
+  }
+  ~TriMesh() { zs_rocm_mesh_destroy(_h); }
+  TriMesh(const TriMesh &) = delete;
+  TriMesh &operator=(const TriMesh &) = delete;
+  template <class Pol> void refit(const Pol &pol, const Vector<float> &verts, const Vector<float> *vel = nullptr) {
+    if (zs_rocm_mesh_refit(pol.handle(), _h, verts.data(), vel ? vel->data() : nullptr) != 0) throw std::runtime_error("TriMesh::refit failed");
+  }
+  TriMeshView view() const {
+    zs_rocm_mesh_view v;
+    zs_rocm_mesh_get_view(_h, &v);
+    TriMeshView r;
+    r.verts = v.verts; r.tris = v.tris; r.vel = v.vel;
+    r.faceNormals = v.faceNormals; r.vertNormals = v.vertNormals; r.edgeNormals = v.edgeNormals;
+    r.bvh.orderedBvs = (const zsr::AABB3 *)v.bvh.orderedBvs; r.bvh.parents = v.bvh.parents; r.bvh.levels = v.bvh.levels;
+    r.bvh.leafInds = v.bvh.leafInds; r.bvh.auxIndices = v.bvh.auxIndices; r.bvh.numNodes = v.bvh.numNodes;
+    r.numVerts = v.numVerts; r.numTris = v.numTris;
+    return r;
+  }
+  zs_rocm_mesh *handle() const { return _h; }
+  zs_rocm_mesh *_h;
+};
+
 // view<space>(container) / proxy<space>(container)  (container/Vector.hpp:455-615, TileVector.hpp:693-1540, Bht.hpp:403)
 template <execspace_e space, class T> VectorView<T> view(Vector<T> &v) {
   static_assert(space == execspace_e::rocm, "this header provides the rocm space only");
@@ -738,6 +778,7 @@ template <execspace_e space, class Tn, int dim, class Ix, int B> BHTView<dim> vi
 template <execspace_e space, int dim> HashTableView<dim> view(HashTable<dim> &t) { return t.view(); }
 template <execspace_e space, int dim, class T, int Side> SparseGridView<dim, T, Side> view(SparseGrid<dim, T, Side> &g) { return g.view(); }
 template <execspace_e space> LBvhView view(const LBvh &b) { return b.view(); }
+template <execspace_e space> TriMeshView view(const TriMesh &m) { return m.view(); }
 template <execspace_e space, class C> auto proxy(C &c) { return view<space>(c); }
 template <execspace_e space, class T, int L> auto proxy(std::initializer_list<const char *> l, TileVector<T, L> &v) { return view<space>(l, v); }
 }  // namespace zs

@@ -732,6 +732,67 @@ ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_solve_levelset(zs_rocm_policy *, const z
                                                        const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount,
                                                        const int *nbr, const zs_rocm_collider *collider, const zs_rocm_levelset *,
                                                        const float *b, float *x, int maxIters, float tol, float relTol, int *iters);
+/* ---- triangle meshes as colliders (include/zensim_rocm/mesh_device.hpp, zpc_amd/csrc/mesh.hip): the bulk form of
+ * `pol(range(n), [bvh = proxy<space>(bvh)](i){ bvh.find_nearest(p, f, cap); })` (LBvhView::find_nearest, container/Bvh.hpp:547-590) with the
+ * point-triangle distance of geometry/SpatialQuery.hpp:19-315 (dist_pt_sqr / pt_category_and_dist2) as the functor f, and the conversion
+ * of a mesh into the SparseGrid<3, f32, 8> level set of zs_rocm_levelset (the reference does this through OpenVDB,
+ * geometry/VdbLevelSet_*.cpp).  The object copies verts [nv][3] f32, tris [nt][3] i32 and the optional per-vertex velocities [nv][3] f32
+ * (NULL: none) from device memory and owns: an LBvh over the triangle boxes (zs_rocm_lbvh_build), unit face normals, angle-weighted vertex
+ * pseudonormals and edge pseudonormals (sum of the adjacent face normals; an edge with one face: that face's normal).  Edge adjacency:
+ * 3 nt half-edge keys (min vertex, max vertex) sorted as u64; vertex sums: corners sorted by vertex, each vertex folds its run in that
+ * order -- the same mesh gives the same bits on every run.  Vertex indices outside [0, nv) are clamped and counted.
+ * Sign of the distance: (p - closest) . pseudonormal(feature) (Baerentzen & Aanaes 2005); features: 0..2 vertex a/b/c, 3..5 edge ab/bc/ca,
+ * 6 face.  Int-returning calls validate their arguments and return -1 with nothing written, else 0. */
+typedef struct zs_rocm_mesh zs_rocm_mesh;
+typedef struct {
+  const float *verts;
+  const int *tris;
+  const float *vel; /* NULL without velocities */
+  const float *faceNormals, *vertNormals, *edgeNormals; /* [nt][3], [nv][3], [nt][3 edges][3] */
+  zs_rocm_lbvh_view bvh;
+  int numVerts, numTris;
+} zs_rocm_mesh_view;
+#define ZS_ROCM_MESH_STAT_WORDS 8
+ZS_ROCM_EXPORT zs_rocm_mesh *zs_rocm_mesh_create(zs_rocm_policy *, const float *verts, size_t nv, const int *tris, size_t nt, const float *vel);
+ZS_ROCM_EXPORT void zs_rocm_mesh_destroy(zs_rocm_mesh *);
+/* new vertex positions (and velocities: NULL keeps the old ones) on the same topology: LBvh::refit (Bvh.hpp:1219-1248) + the normals */
+ZS_ROCM_EXPORT int zs_rocm_mesh_refit(zs_rocm_policy *, zs_rocm_mesh *, const float *verts, const float *vel);
+/* out (host, ZS_ROCM_MESH_STAT_WORDS ints): [0] boundary edges (one face), [1] non-manifold edges (more than two faces), [2] edge pairs
+ * whose two faces run along the edge in the same direction, [3] zero-area triangles, [4] vertex indices out of range; synchronises */
+ZS_ROCM_EXPORT void zs_rocm_mesh_stats(zs_rocm_policy *, const zs_rocm_mesh *, int *out);
+/* box6 (host): LBvh::getTotalBox of the triangle boxes (Bvh.hpp:152-171); synchronises; -1 for a mesh without triangles */
+ZS_ROCM_EXPORT int zs_rocm_mesh_total_box(zs_rocm_policy *, const zs_rocm_mesh *, float *box6);
+/* all zero for a NULL mesh */
+ZS_ROCM_EXPORT void zs_rocm_mesh_get_view(const zs_rocm_mesh *, zs_rocm_mesh_view *out);
+/* bulk find_nearest at points [nq][3]: dist[nq], tri[nq], feature[nq], bary[nq][3]; each output may be NULL.  No triangle nearer than
+ * cap: dist = cap, tri = feature = -1.  16384 or more points are walked in Morton order of the points, like zs_rocm_lbvh_query_*. */
+ZS_ROCM_EXPORT int zs_rocm_mesh_closest_point(zs_rocm_policy *, const zs_rocm_mesh *, const float *points, size_t nq, float cap, float *dist,
+                                              int *tri, int *feature, float *bary);
+/* sdf[nq] = signed distance (+cap when none is nearer), vel[nq][3] = the vertex velocities interpolated at the closest point; either may
+ * be NULL */
+ZS_ROCM_EXPORT int zs_rocm_mesh_signed_distance(zs_rocm_policy *, const zs_rocm_mesh *, const float *points, size_t nq, float cap, float *sdf,
+                                                float *vel);
+/* mesh -> level set.  Cell (i, j, k) sits at origin + voxel (i, j, k) (origin: 3 host floats); the result is what a dense sampling keeps:
+ * every 8^3 block with a cell |sdf| < band, all 512 cells of it the signed distance.  The caller owns every container and sizes it from
+ * the two counts the calls return:
+ *   count       sum over the triangles of the blocks their boxes, dilated by band, touch (synchronises): with the number of blocks in
+ *               the mesh's dilated total box, an upper bound for the candidates
+ *   candidates  inserts those blocks (keys = block origins, multiples of 8) into `cand`, a bht<int, 3, int, 16>
+ *   blocks      one workgroup per candidate, lane = cell: tiles [ncand] x numChannels x 512 (numChannels 1: sdf; 4: sdf, v) and
+ *               keep[ncand] = 1 where a cell has |sdf| < band.  The tree is culled once per block against the block's box and the
+ *               surviving triangles are staged in LDS; a block with more survivors than the stage holds walks the tree per lane.
+ *               stats: NULL or 4 device words ADDED to: [0] blocks rejected by their centre's distance, [1] staged, [2] per-lane, [3] kept
+ *   select      keptKeys [<= ncand][3] = keys of the kept blocks; returns their number (synchronises)
+ *   gather      the kept blocks' tiles to the place `table` (the final bht, holding exactly the kept keys) gives them */
+ZS_ROCM_EXPORT size_t zs_rocm_mesh_levelset_count(zs_rocm_policy *, const zs_rocm_mesh *, const float *origin, float voxel, float band);
+ZS_ROCM_EXPORT int zs_rocm_mesh_levelset_candidates(zs_rocm_policy *, const zs_rocm_mesh *, const float *origin, float voxel, float band,
+                                                    zs_rocm_bht_3 *cand);
+ZS_ROCM_EXPORT int zs_rocm_mesh_levelset_blocks(zs_rocm_policy *, const zs_rocm_mesh *, const float *origin, float voxel, float band,
+                                                const zs_rocm_bht_3 *cand, size_t ncand, float *tiles, int numChannels, int *keep,
+                                                unsigned *stats);
+ZS_ROCM_EXPORT size_t zs_rocm_mesh_levelset_select(zs_rocm_policy *, const zs_rocm_bht_3 *cand, size_t ncand, const int *keep, int *keptKeys);
+ZS_ROCM_EXPORT int zs_rocm_mesh_levelset_gather(zs_rocm_policy *, const zs_rocm_bht_3 *cand, size_t ncand, const int *keep, const float *tiles,
+                                                const zs_rocm_bht_3 *table, float *dstTiles, int numChannels);
 /* ---- slotted particle storage: the motion-robust form of the fused step (zpc_amd/csrc/mpm_slotted.hip).  Storage = bins x K rounds x
  * 64 lanes in ONE TileVector<f32, 64> (slot (bin, r, lane) = element (bin K + r) 64 + lane), cellMask[bin][lane] = occupied rounds of the
  * cell; a particle is always stored under the cell of its base node, and the step keeps it so.  A particle that changes cell is finished

@@ -115,6 +115,12 @@ class LevelSet(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+class MeshView(C.Structure):
+    """zs_rocm_mesh_view (include/zs_rocm.h): the arrays of a triangle mesh object, all device pointers"""
+    _fields_ = [("verts", C.c_void_p), ("tris", C.c_void_p), ("vel", C.c_void_p), ("faceNormals", C.c_void_p), ("vertNormals", C.c_void_p),
+                ("edgeNormals", C.c_void_p), ("bvh", LBvhView), ("numVerts", C.c_int), ("numTris", C.c_int)]
+
+
 def _declare(L):
     vp, sz, i32, f32 = C.c_void_p, C.c_size_t, C.c_int, C.c_float
     L.policy__device.restype = vp
@@ -423,6 +429,28 @@ def _declare_containers(L):
     for name in ("levelset_sample", "levelset_collider_resolve", "mpm_apply_boundary_levelset", "mpm_implicit_project_levelset",
                  "mpm_implicit_solve_levelset"):
         getattr(L, "zs_rocm_" + name).restype = i32
+    L.zs_rocm_mesh_create.argtypes = [vp, vp, sz, vp, sz, vp]
+    L.zs_rocm_mesh_create.restype = vp
+    L.zs_rocm_mesh_destroy.argtypes = [vp]
+    L.zs_rocm_mesh_destroy.restype = None
+    L.zs_rocm_mesh_refit.argtypes = [vp, vp, vp, vp]
+    L.zs_rocm_mesh_stats.argtypes = [vp, vp, C.POINTER(C.c_int)]
+    L.zs_rocm_mesh_stats.restype = None
+    L.zs_rocm_mesh_total_box.argtypes = [vp, vp, C.POINTER(C.c_float)]
+    L.zs_rocm_mesh_get_view.argtypes = [vp, C.POINTER(MeshView)]
+    L.zs_rocm_mesh_get_view.restype = None
+    L.zs_rocm_mesh_closest_point.argtypes = [vp, vp, vp, sz, f32, vp, vp, vp, vp]
+    L.zs_rocm_mesh_signed_distance.argtypes = [vp, vp, vp, sz, f32, vp, vp]
+    P3 = C.POINTER(C.c_float)
+    L.zs_rocm_mesh_levelset_count.argtypes = [vp, vp, P3, f32, f32]
+    L.zs_rocm_mesh_levelset_count.restype = sz
+    L.zs_rocm_mesh_levelset_candidates.argtypes = [vp, vp, P3, f32, f32, vp]
+    L.zs_rocm_mesh_levelset_blocks.argtypes = [vp, vp, P3, f32, f32, vp, sz, vp, i32, vp, vp]
+    L.zs_rocm_mesh_levelset_select.argtypes = [vp, vp, sz, vp, vp]
+    L.zs_rocm_mesh_levelset_select.restype = sz
+    L.zs_rocm_mesh_levelset_gather.argtypes = [vp, vp, sz, vp, vp, vp, vp, i32]
+    for name in ("refit", "total_box", "closest_point", "signed_distance", "levelset_candidates", "levelset_blocks", "levelset_gather"):
+        getattr(L, "zs_rocm_mesh_" + name).restype = i32
     L.zs_rocm_dof_assign.argtypes = [vp, vp, vp, sz]
     L.zs_rocm_dof_assign.restype = None
     L.zs_rocm_dof_fill.argtypes = [vp, vp, f32, sz]

@@ -27,7 +27,10 @@ EXTRA_FLAGS = {"mpm_slotted.hip": ["-fno-slp-vectorize"], "mpm_slotblk.hip": ["-
                # finite-difference normals of the analytic colliders (eps = 1e-6 in float) must round like the reference's
                "collider.hip": ["-ffp-contract=off"], "mpm_implicit_project.hip": ["-ffp-contract=off"],
                # the level-set normal is a float central difference at +- h / 4 (include/zensim_rocm/levelset_device.hpp)
-               "levelset.hip": ["-ffp-contract=off"]}
+               "levelset.hip": ["-ffp-contract=off"],
+               # point-triangle distances and pseudonormal signs (include/zensim_rocm/distance_device.hpp): a float32 chain in numpy
+               # reproduces the discrete decisions (region, nearest triangle, sign) only without fused multiply-adds
+               "mesh.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst):
@@ -111,6 +114,22 @@ def build_levelset_test(verbose=True):
     return out
 
 
+def build_mesh_test(verbose=True):
+    """tests/cpp/test_mesh.hip: TriMeshView::signed_distance / closest_point in a user lambda against the C ABI's bulk entries; built
+    without FP contraction like every translation unit that uses the point-triangle distance."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_mesh.hip")
+    out = os.path.join(LIBDIR, "test_mesh")
+    face = os.path.join(ROOT, "include", "zensim_rocm")
+    deps = [src, LIB] + [os.path.join(face, f) for f in os.listdir(face) if f.endswith(".hpp")]
+    if os.path.exists(src) and any(_newer(d, out) for d in deps):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), src,
+               "-L", LIBDIR, "-lzsrocm", "-Wl,-rpath,$ORIGIN", "-o", out]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return out
+
+
 def build_oracle(verbose=True):
     """CPU restatement (always) and, where /root/reference exists, the in-place build of the reference's
     header-only numerics (oracle/_ref).  Building the checker is not using it."""
@@ -126,4 +145,5 @@ if __name__ == "__main__":
     build_cpp_face_test()
     build_ofb_test()
     build_levelset_test()
+    build_mesh_test()
     build_oracle()

@@ -63,6 +63,7 @@ class SparseLevelSet:
             lib().zs_rocm_tv_from_aos_f32(pol.handle, dc.data_ptr(), nb * BLOCK, nch, BLOCK, self.tiles.data())
             pol.syncCtx()
         self.stats = None
+        self.band = None   # set by from_dense / from_mesh (update_from_mesh needs it)
         self._make_view()
 
     def _make_view(self):
@@ -86,7 +87,9 @@ class SparseLevelSet:
         to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
         background = band if background is None else background
         keys, cells = select_blocks(to_np(sdf), band, background, None if vel is None else to_np(vel))
-        return cls(pol, keys, cells, origin, voxel, background)
+        self = cls(pol, keys, cells, origin, voxel, background)
+        self.band = float(band)
+        return self
 
     @classmethod
     def from_function(cls, pol, fn, lo, hi, voxel, band, vel_fn=None, background=None):
@@ -95,6 +98,90 @@ class SparseLevelSet:
         n = [int(np.ceil((h - l) / voxel)) + 1 for l, h in zip(lo, hi)]
         x = lo + voxel * np.stack(np.meshgrid(*[np.arange(k) for k in n], indexing="ij"), axis=-1)
         return cls.from_dense(pol, fn(x), lo, voxel, band, vel=None if vel_fn is None else vel_fn(x), background=background)
+
+    @classmethod
+    def from_mesh(cls, pol, mesh, voxel, band, origin=None, background=None, allow_open=False):
+        """The level set of a TriMesh, built on the device: what from_dense makes of the mesh's signed distance sampled at
+        origin + voxel * (i, j, k) -- every 8^3 block with a cell |sdf| < band, all 512 cells of it the signed distance, blocks numbered in
+        lexicographic key order; with vertex velocities the tiles carry "v".  origin defaults to the mesh's total box minus band, snapped
+        down to a multiple of voxel; background defaults to band.  The host only sizes the containers."""
+        from .mesh import default_origin
+        if not (voxel > 0 and band > 0):
+            raise ValueError("from_mesh: voxel and band must be positive")
+        if not allow_open and not mesh.is_closed():
+            raise ValueError("from_mesh: the mesh is not closed and consistently oriented (%r); pass allow_open=True to take the "
+                             "pseudonormal sign anyway" % (mesh.stats(),))
+        if origin is None:
+            origin = default_origin(mesh.total_box()[0], voxel, band)
+        self = cls.__new__(cls)
+        self.pol = pol
+        self.origin = tuple(float(v) for v in origin)
+        self.voxel, self.band = float(voxel), float(band)
+        self.background = float(band if background is None else background)
+        self.has_velocity = bool(mesh.has_velocity)
+        self.stats = None
+        self.build_stats = None
+        self.update_from_mesh(mesh)
+        return self
+
+    def update_from_mesh(self, mesh):
+        """rebuild in place from the mesh's current vertices (after TriMesh.refit): same origin, voxel, band and channels"""
+        import torch
+        from .mesh import candidate_capacity
+        L, pol = lib(), self.pol
+        if bool(mesh.has_velocity) != self.has_velocity:
+            raise ValueError("update_from_mesh: the mesh's velocities must stay present / absent")
+        nch = 4 if self.has_velocity else 1
+        org = (C.c_float * 3)(*self.origin)
+        if getattr(self, "band", None) is None:
+            raise ValueError("update_from_mesh: this level set does not know its band (built from keys and cells directly)")
+        voxel, band = self.voxel, self.band
+        nkept, keys = 0, np.zeros((0, 3), np.int32)
+        self.build_stats = np.zeros(4, np.int64)
+        if mesh.nt:
+            pairs = L.zs_rocm_mesh_levelset_count(pol.handle, mesh.handle, org, voxel, band)
+            if pairs == C.c_size_t(-1).value:
+                raise ValueError("from_mesh: the lattice is too fine for this mesh (2^31 candidate blocks or more)")
+            lo, hi = mesh.total_box()
+            cand = Bht(3, candidate_capacity(pairs, lo, hi, self.origin, voxel, band), bucket=16)
+            if L.zs_rocm_mesh_levelset_candidates(pol.handle, mesh.handle, org, voxel, band, cand.handle) != 0:
+                raise RuntimeError("zs_rocm_mesh_levelset_candidates failed")
+            pol.syncCtx()
+            ncand = cand.size()
+            if not cand.success():
+                raise RuntimeError("from_mesh: the candidate table overflowed")
+            scratch = torch.empty(max(ncand, 1) * nch * BLOCK, dtype=torch.float32, device="cuda")
+            keep = torch.zeros(max(ncand, 1), dtype=torch.int32, device="cuda")
+            stats = torch.zeros(4, dtype=torch.int32, device="cuda")
+            if L.zs_rocm_mesh_levelset_blocks(pol.handle, mesh.handle, org, voxel, band, cand.handle, ncand, scratch.data_ptr(), nch,
+                                              keep.data_ptr(), stats.data_ptr()) != 0:
+                raise RuntimeError("zs_rocm_mesh_levelset_blocks failed")
+            kept = torch.empty(max(ncand, 1), 3, dtype=torch.int32, device="cuda")
+            nkept = L.zs_rocm_mesh_levelset_select(pol.handle, cand.handle, ncand, keep.data_ptr(), kept.data_ptr())
+            if nkept == C.c_size_t(-1).value:
+                raise RuntimeError("zs_rocm_mesh_levelset_select failed")
+            self.build_stats = stats.cpu().numpy().astype(np.int64)
+        self.nblocks = int(nkept)
+        self.table = Bht(3, max(self.nblocks, 1), bucket=16)
+        tags = [("sdf", 1)] + ([("v", 3)] if self.has_velocity else [])
+        self.tiles = TileVector("float", BLOCK, tags, max(self.nblocks, 1) * BLOCK)
+        if self.nblocks:
+            self.table.insert(pol, kept.data_ptr(), self.nblocks)
+            self.table.canonicalize(pol)   # lexicographic key order: the numbering select_blocks gives
+            if L.zs_rocm_mesh_levelset_gather(pol.handle, cand.handle, ncand, keep.data_ptr(), scratch.data_ptr(), self.table.handle,
+                                              self.tiles.data(), nch) != 0:
+                raise RuntimeError("zs_rocm_mesh_levelset_gather failed")
+            pol.syncCtx()
+            keys = self.active_keys()
+        self.keys = keys
+        self._make_view()
+
+    def active_keys(self):
+        """the block origins in block-number order, read back from the table [nblocks, 3]"""
+        a = np.empty((self.nblocks, 3), np.int32)
+        if self.nblocks:
+            C.CDLL("libamdhip64.so").hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(self.table.view().activeKeys), C.c_size_t(a.nbytes), 2)
+        return a
 
     def enable_stats(self):
         """count, per block-kernel launch and grid block, how the block was handled: stats()[0] culled, [1] staged, [2] direct"""

@@ -1,0 +1,151 @@
+"""Triangle meshes as colliders: TriMesh owns a device mesh object of the library (LBvh over the triangle boxes, face normals, vertex and
+edge pseudonormals) and answers closest-point and signed-distance queries; SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
+into a sparse level set.  Set-up code: torch for the plumbing; every query runs in the library's HIP kernels."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import lib, MeshView
+
+FEATURES = ("vertex a", "vertex b", "vertex c", "edge ab", "edge bc", "edge ca", "face")
+STAT_NAMES = ("boundary_edges", "nonmanifold_edges", "inconsistent_edges", "zero_area_triangles", "bad_indices")
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def default_origin(box_lo, voxel, band):
+    """origin of from_mesh: the mesh's total box minus band, snapped down to a multiple of voxel (host logic, no device needed)"""
+    lo = np.asarray(box_lo, np.float64) - float(band)
+    return tuple(float(v) for v in np.floor(lo / float(voxel)) * float(voxel))
+
+
+def candidate_capacity(pairs, box_lo, box_hi, origin, voxel, band):
+    """upper bound for the candidate blocks of from_mesh: the (triangle, block) pairs, or the blocks under the mesh's total box dilated by
+    band and one cell, whichever is smaller (host logic)"""
+    lo = np.floor((np.asarray(box_lo, np.float64) - np.asarray(origin, np.float64) - band) / voxel) - 2
+    hi = np.ceil((np.asarray(box_hi, np.float64) - np.asarray(origin, np.float64) + band) / voxel) + 2
+    nb = np.floor(hi / 8) - np.floor(lo / 8) + 1
+    return int(max(1, min(float(pairs), float(np.prod(nb)))))
+
+
+def _dev_f32(a, cols):
+    import torch
+    t = a if hasattr(a, "detach") else torch.from_numpy(np.ascontiguousarray(a, np.float32))
+    t = t.to(device="cuda", dtype=torch.float32).contiguous()
+    if t.ndim != 2 or t.shape[1] != cols:
+        raise ValueError("expected an [n, %d] array" % cols)
+    return t
+
+
+class TriMesh:
+    """TriMesh(pol, verts [nv, 3] f32, tris [nt, 3] i32, vel=None [nv, 3] f32): arrays on the host or the device; the object keeps copies."""
+
+    def __init__(self, pol, verts, tris, vel=None):
+        import torch
+        self.pol = pol
+        v = _dev_f32(verts, 3)
+        t = tris if hasattr(tris, "detach") else torch.from_numpy(np.ascontiguousarray(tris, np.int32).reshape(-1, 3))
+        t = t.to(device="cuda", dtype=torch.int32).contiguous()
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("tris: [nt, 3]")
+        w = None if vel is None else _dev_f32(vel, 3)
+        if w is not None and w.shape != v.shape:
+            raise ValueError("vel: [nv, 3]")
+        self.nv, self.nt = int(v.shape[0]), int(t.shape[0])
+        self.has_velocity = w is not None
+        self._h = lib().zs_rocm_mesh_create(pol.handle, v.data_ptr(), self.nv, t.data_ptr(), self.nt, None if w is None else w.data_ptr())
+        if not self._h:
+            raise ValueError("TriMesh: triangles without vertices, or too many of either")
+        pol.syncCtx()   # the inputs are copied by now
+        if self.stats()["bad_indices"]:
+            raise ValueError("TriMesh: vertex indices outside [0, %d)" % self.nv)
+
+    def __del__(self):
+        try:
+            lib().zs_rocm_mesh_destroy(self._h)
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def view(self):
+        v = MeshView()
+        lib().zs_rocm_mesh_get_view(self._h, C.byref(v))
+        return v
+
+    def stats(self):
+        out = (C.c_int * 8)()
+        lib().zs_rocm_mesh_stats(self.pol.handle, self._h, out)
+        return {k: int(out[i]) for i, k in enumerate(STAT_NAMES)}
+
+    def is_closed(self):
+        """closed and consistently oriented: what the pseudonormal sign needs"""
+        s = self.stats()
+        return self.nt > 0 and not (s["boundary_edges"] or s["nonmanifold_edges"] or s["inconsistent_edges"])
+
+    def total_box(self):
+        box = (C.c_float * 6)()
+        if lib().zs_rocm_mesh_total_box(self.pol.handle, self._h, box) != 0:
+            raise ValueError("TriMesh.total_box: a mesh without triangles")
+        return np.array(box[:3], np.float32), np.array(box[3:], np.float32)
+
+    def refit(self, verts, vel=None):
+        """new vertex positions (and velocities) on the same topology: refits the tree and recomputes the normals"""
+        v = _dev_f32(verts, 3)
+        w = None if vel is None else _dev_f32(vel, 3)
+        if v.shape[0] != self.nv or (w is not None and w.shape[0] != self.nv):
+            raise ValueError("TriMesh.refit: the topology is kept, so the vertex count must not change")
+        if lib().zs_rocm_mesh_refit(self.pol.handle, self._h, v.data_ptr(), None if w is None else w.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mesh_refit failed")
+        self.pol.syncCtx()
+        self.has_velocity = self.has_velocity or w is not None
+
+    @staticmethod
+    def _cap(cap):
+        return FLT_MAX if cap is None or not np.isfinite(cap) else float(cap)
+
+    def closest_point(self, points, cap=float("inf")):
+        """(dist [n], tri [n], feature [n], bary [n, 3]) as torch tensors on the device; no triangle nearer than cap: dist = cap (the
+        largest float for cap = inf), tri = feature = -1"""
+        import torch
+        p = _dev_f32(points, 3)
+        n = int(p.shape[0])
+        dist = torch.empty(n, dtype=torch.float32, device="cuda")
+        tri = torch.empty(n, dtype=torch.int32, device="cuda")
+        feat = torch.empty(n, dtype=torch.int32, device="cuda")
+        bary = torch.empty(n, 3, dtype=torch.float32, device="cuda")
+        if lib().zs_rocm_mesh_closest_point(self.pol.handle, self._h, p.data_ptr(), n, self._cap(cap), dist.data_ptr(), tri.data_ptr(),
+                                            feat.data_ptr(), bary.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mesh_closest_point failed")
+        self.pol.syncCtx()
+        return dist, tri, feat, bary
+
+    def signed_distance(self, points, cap=float("inf"), signed=True, allow_open=False):
+        """(sdf [n], vel [n, 3] or None); signed=True needs a closed, consistently oriented mesh unless allow_open"""
+        import torch
+        if signed and not allow_open and not self.is_closed():
+            raise ValueError("TriMesh.signed_distance: the mesh is not closed and consistently oriented (%r); pass allow_open=True to take "
+                             "the pseudonormal sign anyway" % (self.stats(),))
+        p = _dev_f32(points, 3)
+        n = int(p.shape[0])
+        sdf = torch.empty(n, dtype=torch.float32, device="cuda")
+        vel = torch.empty(n, 3, dtype=torch.float32, device="cuda") if self.has_velocity else None
+        if lib().zs_rocm_mesh_signed_distance(self.pol.handle, self._h, p.data_ptr(), n, self._cap(cap), sdf.data_ptr(),
+                                              None if vel is None else vel.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mesh_signed_distance failed")
+        self.pol.syncCtx()
+        return (sdf if signed else sdf.abs()), vel
+
+    def normals(self):
+        """(face [nt, 3], vertex [nv, 3], edge [nt, 3, 3]) copied to the host (tests)"""
+        v = self.view()
+        hip = C.CDLL("libamdhip64.so")
+
+        def fetch(ptr, shape):
+            a = np.empty(shape, np.float32)
+            if a.size:
+                hip.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(ptr), C.c_size_t(a.nbytes), 2)
+            return a
+        self.pol.syncCtx()
+        return fetch(v.faceNormals, (self.nt, 3)), fetch(v.vertNormals, (self.nv, 3)), fetch(v.edgeNormals, (self.nt, 3, 3))
