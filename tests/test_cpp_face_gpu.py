@@ -13,7 +13,7 @@ def test_cpp_face_program_runs():
     exe = os.path.join(ROOT, "zpc_amd", "lib", "test_cpp_face")
     if not os.path.exists(exe):
         from zpc_amd import build
-        build.build_cpp_face_test()
+        build.build_cpp_test("test_cpp_face")
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     assert r.returncode == 0 and b"cpp face ok" in r.stdout, r.stdout.decode()
 
@@ -37,7 +37,7 @@ def test_grid_arena_matches_the_references_own_grid_arena(tmp_path):
     exe = os.path.join(ROOT, "zpc_amd", "lib", "test_cpp_face")
     if not os.path.exists(exe):
         from zpc_amd import build
-        build.build_cpp_face_test()
+        build.build_cpp_test("test_cpp_face")
     r = subprocess.run([exe, "--grid-arena", str(blob)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     assert r.returncode == 0 and b" 0 mismatches" in r.stdout, r.stdout.decode()[-3000:]
 
@@ -47,6 +47,6 @@ def test_views_with_the_ofb_access_check_option():
     exe = os.path.join(ROOT, "zpc_amd", "lib", "test_ofb")
     if not os.path.exists(exe):
         from zpc_amd import build
-        build.build_ofb_test()
+        build.build_cpp_test("test_ofb")
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     assert r.returncode == 0 and b"ofb access checks: 0 failures" in r.stdout, r.stdout.decode()[-2000:]

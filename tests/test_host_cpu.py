@@ -9,6 +9,8 @@ import sys
 import numpy as np
 import pytest
 
+from util import LLVM_BIN, code_object_kernels
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -285,22 +287,17 @@ def test_small_input_sort_kernels_use_no_scratch_memory(tmp_path):
     results ("radix sort, up to 2 M 4-byte keys").  Read from the built code object's metadata."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     obj = os.path.join(root, "zpc_amd", "lib", "obj", "primitives.o")
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not (os.path.exists(obj) and os.path.exists(os.path.join(llvm, "clang-offload-bundler"))):
+    found = code_object_kernels(obj, tmp_path)
+    if found is None:
         pytest.skip("object file or llvm tools not present")
-    fat, co = str(tmp_path / "p.fat"), str(tmp_path / "p.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
-    subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat,
-                           "--output=" + co, "--unbundle"])
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], stdout=subprocess.PIPE, check=True).stdout.decode()
+    kernels, co = found
     seen = 0
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk)
-        if not name or "radix_small" not in name.group(1):
+    for name, meta, _ in kernels:
+        if "radix_small" not in name:
             continue
         seen += 1
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, name.group(1)
-        assert re.search(r"\.uses_dynamic_stack:\s+(\w+)", blk).group(1) == "false", name.group(1)
+        assert int(meta[".private_segment_fixed_size"]) == 0, name
+        assert meta[".uses_dynamic_stack"] == "false", name
     assert seen >= 12  # hist x 4 key types, split and finish x 4 key types x {keys, pairs} (minus duplicates the linker folds)
 
 
@@ -311,21 +308,16 @@ def test_merge_sort_kernels_of_the_cpp_face_use_no_scratch_memory(tmp_path):
     r05 removed the private memory from the merge kernels (merge_sort.hpp: serial_merge); this keeps it removed."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "zpc_amd", "lib", "test_cpp_face")
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not (os.path.exists(exe) and os.path.exists(os.path.join(llvm, "clang-offload-bundler"))):
+    found = code_object_kernels(exe, tmp_path)
+    if found is None:
         pytest.skip("test program or llvm tools not present")
-    fat, co = str(tmp_path / "p.fat"), str(tmp_path / "p.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", exe, fat])
-    subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat,
-                           "--output=" + co, "--unbundle"])
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], stdout=subprocess.PIPE, check=True).stdout.decode()
+    kernels, co = found
     seen = 0
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk)
-        if not name or "zs_rocm_ms" not in name.group(1):
+    for name, meta, _ in kernels:
+        if "zs_rocm_ms" not in name:
             continue
         seen += 1
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, name.group(1)
+        assert int(meta[".private_segment_fixed_size"]) == 0, name
     assert seen >= 6  # tile sort, partition and merge kernels for int keys, pairs and the struct key
 
 
@@ -337,26 +329,20 @@ def test_block_kernel_of_the_fused_step_keeps_its_chunk_loop_free_of_scratch(tmp
     (the wave number is a run-time value: 54 KB, not 87-94 KB)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     obj = os.path.join(root, "zpc_amd", "lib", "obj", "mpm_slotblk.o")
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not (os.path.exists(obj) and os.path.exists(os.path.join(llvm, "clang-offload-bundler"))):
+    found = code_object_kernels(obj, tmp_path)
+    if found is None:
         pytest.skip("object file or llvm tools not present")
-    fat, co = str(tmp_path / "p.fat"), str(tmp_path / "p.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
-    subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat,
-                           "--output=" + co, "--unbundle"])
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], stdout=subprocess.PIPE, check=True).stdout.decode()
+    kernels, co = found
     seen = 0
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk)
-        m = name and re.search(r"g2p2g_slotblk_kernelILi(\d)ELb", name.group(1))
+    for name, meta, _ in kernels:
+        m = re.search(r"g2p2g_slotblk_kernelILi(\d)ELb", name)
         if not m or int(m.group(1)) > 3:  # 0 fixed-corotated, 1 DruckerPrager, 2 von Mises, 3 NACC (4 = the fluid: not covered)
             continue
         seen += 1
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, name.group(1)
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 128, name.group(1)
+        assert int(meta[".private_segment_fixed_size"]) == 0, name
+        assert int(meta[".vgpr_count"]) <= 128, name
     assert seen == 8  # four models x {write everything, write the step's state only}
-    syms = subprocess.run([os.path.join(llvm, "llvm-readelf"), "-sW", co], stdout=subprocess.PIPE, check=True).stdout.decode()
-    sizes = [int(l.split()[2]) for l in syms.splitlines() if "g2p2g_slotblk_kernelILi1ELb0" in l and " FUNC " in l]
+    sizes = [size for name, _, size in kernels if "g2p2g_slotblk_kernelILi1ELb0" in name]
     assert sizes and max(sizes) < 64 * 1024, sizes
 
 
@@ -368,25 +354,20 @@ def test_tile_kernel_of_the_standalone_p2g_keeps_its_accumulators_in_registers_a
     directly in front of a `ds_read`."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     obj = os.path.join(root, "zpc_amd", "lib", "obj", "mpm_p2g.o")
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not (os.path.exists(obj) and os.path.exists(os.path.join(llvm, "clang-offload-bundler"))):
+    found = code_object_kernels(obj, tmp_path)
+    if found is None:
         pytest.skip("object file or llvm tools not present")
-    fat, co = str(tmp_path / "p.fat"), str(tmp_path / "p.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
-    subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat,
-                           "--output=" + co, "--unbundle"])
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], stdout=subprocess.PIPE, check=True).stdout.decode()
+    kernels, co = found
     seen = 0
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk)
-        if not name or "p2g_tile_kernel" not in name.group(1):
+    for name, meta, _ in kernels:
+        if "p2g_tile_kernel" not in name:
             continue
         seen += 1
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, name.group(1)
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, name.group(1)
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= 256, name.group(1)
+        assert int(meta[".private_segment_fixed_size"]) == 0, name
+        assert int(meta[".vgpr_spill_count"]) == 0, name
+        assert int(meta[".vgpr_count"]) <= 256, name
     assert seen >= 4  # 8^3 blocks (two bins per workgroup) and 4^3 blocks, merged and per-attribute requests
-    dis = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", co], stdout=subprocess.PIPE, check=True).stdout.decode()
+    dis = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", co], stdout=subprocess.PIPE, check=True).stdout.decode()
     m = re.search(r"<_ZN3zsrL15p2g_tile_kernelILi8ELi3ELi2ELb1E[^>]*>:\n(.*?)s_endpgm", dis, re.S)
     assert m, "p2g_tile_kernel<8, 3, 2, true> not found"
     lines = [l.split("//")[0].strip() for l in m.group(1).splitlines() if l.strip()]

@@ -444,7 +444,7 @@ def test_cpp_face_levelset_collider_program_runs():
     exe = os.path.join(ROOT, "zpc_amd", "lib", "test_levelset")
     if not os.path.exists(exe):
         from zpc_amd import build
-        build.build_levelset_test()
+        build.build_cpp_test("test_levelset")
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     print(r.stdout.decode()[-1500:])
     assert r.returncode == 0 and b"levelset cpp face ok: 0 mismatches" in r.stdout, r.stdout.decode()[-3000:]

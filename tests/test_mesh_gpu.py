@@ -363,7 +363,7 @@ def test_cpp_face_mesh_view(pol):
     exe = os.path.join(ROOT, "zpc_amd", "lib", "test_mesh")
     if not os.path.exists(exe):
         from zpc_amd import build
-        build.build_mesh_test()
+        build.build_cpp_test("test_mesh")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     print(out.stdout)
     assert out.returncode == 0, out.stdout + out.stderr

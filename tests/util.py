@@ -1,5 +1,8 @@
 """Shared helpers for the parity tests: seeded inputs (xorshift64*) and oracle wrappers."""
 import ctypes as C
+import os
+import re
+import subprocess
 
 import numpy as np
 
@@ -311,3 +314,29 @@ def golden_c2(name, side):
     return dict(model=GOLDEN_MODELS[name], side=side, dx=float(z["dx"]), dt=float(z["dt"]), volume=float(prm[0]), kw=kw, keys=z["keys_s%d" % side],
                 mass=z["mass"], pos=z["pos"], vel=z["vel"], B=z["B"], F=F, grid=z["grid_%s_s%d" % (name, side)], gridv=z["gridv_s%d" % side],
                 vel1=z["g2c2p_vel_s%d" % side], B1=z["g2c2p_B_s%d" % side])
+
+
+LLVM_BIN = "/opt/rocm/lib/llvm/bin"
+
+
+def code_object_kernels(obj, workdir, co_name="p.co"):
+    """The gfx950 kernels of a built object file or program: (kernel name, metadata dict, symbol size) per kernel, and the path of the
+    unbundled code object (for a disassembly).  objcopy takes the fat binary out of `obj`, clang-offload-bundler the gfx950 code object
+    out of that, llvm-readelf its notes and symbols; the metadata values stay strings (".vgpr_count" -> "128").  None if `obj` or the
+    llvm tools are missing."""
+    bundler = os.path.join(LLVM_BIN, "clang-offload-bundler")
+    if not (os.path.exists(obj) and os.path.exists(bundler)):
+        return None
+    fat, co = os.path.join(str(workdir), co_name + ".fat"), os.path.join(str(workdir), co_name)
+    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
+    subprocess.check_call([bundler, "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co, "--unbundle"])
+    readelf = os.path.join(LLVM_BIN, "llvm-readelf")
+    notes = subprocess.run([readelf, "--notes", co], stdout=subprocess.PIPE, check=True).stdout.decode()
+    syms = subprocess.run([readelf, "-sW", co], stdout=subprocess.PIPE, check=True).stdout.decode()
+    size = {f[7]: int(f[2]) for f in (l.split() for l in syms.splitlines()) if len(f) == 8 and f[3] == "FUNC"}
+    kernels = []
+    for blk in notes.split("- .agpr_count:")[1:]:
+        meta = dict(re.findall(r"^\s+(\.\w+):\s+(\S+)\s*$", "    .agpr_count:" + blk, re.M))
+        if ".name" in meta:
+            kernels.append((meta[".name"], meta, size[meta[".name"]]))
+    return kernels, co

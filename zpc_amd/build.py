@@ -67,15 +67,25 @@ def build_hip(force=False, verbose=True):
     return LIB
 
 
-def build_cpp_face_test(verbose=True):
-    """tests/cpp/test_cpp_face.hip: a user translation unit written against the header-only C++ face
-    (include/zensim_rocm/zs_rocm.hpp) -- proves that the face compiles with hipcc and links libzsrocm.so."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_cpp_face.hip")
-    out = os.path.join(LIBDIR, "test_cpp_face")
+# Test programs under tests/cpp, each a user translation unit written against the header-only C++ face (include/zensim_rocm) and linked
+# against libzsrocm.so: name -> extra compiler flags.
+#   test_cpp_face   proves that the face compiles with hipcc and links the library
+#   test_ofb        the face compiled with ZS_ENABLE_OFB_ACCESS_CHECK=1 (the reference's bounds-check build option)
+#   test_levelset   Collider{sparseGridView, type}.resolveCollision in a user lambda against the C ABI's level-set entries; built without
+#                   FP contraction like every translation unit that evaluates a level set
+#   test_mesh       TriMeshView::signed_distance / closest_point in a user lambda against the C ABI's bulk entries; built without FP
+#                   contraction like every translation unit that uses the point-triangle distance
+CPP_TESTS = {"test_cpp_face": ["-munsafe-fp-atomics"], "test_ofb": [], "test_levelset": ["-ffp-contract=off"], "test_mesh": ["-ffp-contract=off"]}
+
+
+def build_cpp_test(name, verbose=True):
+    """Compile tests/cpp/<name>.hip (a key of CPP_TESTS) against the C++ face and libzsrocm.so into zpc_amd/lib/<name>; returns that path."""
+    src = os.path.join(ROOT, "tests", "cpp", name + ".hip")
+    out = os.path.join(LIBDIR, name)
     face = os.path.join(ROOT, "include", "zensim_rocm")
     deps = [src, LIB] + [os.path.join(face, f) for f in os.listdir(face) if f.endswith(".hpp")]
     if os.path.exists(src) and any(_newer(d, out) for d in deps):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-munsafe-fp-atomics", "-I", os.path.join(ROOT, "include"), src,
+        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17"] + CPP_TESTS[name] + ["-I", os.path.join(ROOT, "include"), src,
                "-L", LIBDIR, "-lzsrocm", "-Wl,-rpath,$ORIGIN", "-o", out]
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -83,51 +93,8 @@ def build_cpp_face_test(verbose=True):
     return out
 
 
-def build_ofb_test(verbose=True):
-    """tests/cpp/test_ofb.hip: the C++ face compiled with ZS_ENABLE_OFB_ACCESS_CHECK=1 (the reference's bounds-check build option)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_ofb.hip")
-    out = os.path.join(LIBDIR, "test_ofb")
-    face = os.path.join(ROOT, "include", "zensim_rocm")
-    deps = [src, LIB] + [os.path.join(face, f) for f in os.listdir(face) if f.endswith(".hpp")]
-    if os.path.exists(src) and any(_newer(d, out) for d in deps):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-L", LIBDIR, "-lzsrocm",
-               "-Wl,-rpath,$ORIGIN", "-o", out]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-    return out
-
-
-def build_levelset_test(verbose=True):
-    """tests/cpp/test_levelset.hip: Collider{sparseGridView, type}.resolveCollision in a user lambda against the C ABI's level-set
-    entries; built without FP contraction like every translation unit that evaluates a level set."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_levelset.hip")
-    out = os.path.join(LIBDIR, "test_levelset")
-    face = os.path.join(ROOT, "include", "zensim_rocm")
-    deps = [src, LIB] + [os.path.join(face, f) for f in os.listdir(face) if f.endswith(".hpp")]
-    if os.path.exists(src) and any(_newer(d, out) for d in deps):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), src,
-               "-L", LIBDIR, "-lzsrocm", "-Wl,-rpath,$ORIGIN", "-o", out]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-    return out
-
-
-def build_mesh_test(verbose=True):
-    """tests/cpp/test_mesh.hip: TriMeshView::signed_distance / closest_point in a user lambda against the C ABI's bulk entries; built
-    without FP contraction like every translation unit that uses the point-triangle distance."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_mesh.hip")
-    out = os.path.join(LIBDIR, "test_mesh")
-    face = os.path.join(ROOT, "include", "zensim_rocm")
-    deps = [src, LIB] + [os.path.join(face, f) for f in os.listdir(face) if f.endswith(".hpp")]
-    if os.path.exists(src) and any(_newer(d, out) for d in deps):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), src,
-               "-L", LIBDIR, "-lzsrocm", "-Wl,-rpath,$ORIGIN", "-o", out]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-    return out
+def build_cpp_tests(verbose=True):
+    return [build_cpp_test(name, verbose) for name in CPP_TESTS]
 
 
 def build_oracle(verbose=True):
@@ -142,8 +109,5 @@ def build_oracle(verbose=True):
 if __name__ == "__main__":
     force = "--force" in sys.argv
     print(build_hip(force=force))
-    build_cpp_face_test()
-    build_ofb_test()
-    build_levelset_test()
-    build_mesh_test()
+    build_cpp_tests()
     build_oracle()

@@ -1,6 +1,7 @@
 #pragma once
 // mpm_arena.hpp -- device code shared by the stand-alone transfers (mpm_p2g_kernels.hpp, mpm_g2p_kernels.hpp) and the fused steps
-// (mpm_fused_kernels.hpp, mpm_slot.hpp): bins and their LDS arenas, the round-robin walk, the G2P gather from an arena, the tail of G2P
+// (mpm_fused_kernels.hpp, mpm_slot.hpp): bins and their LDS arenas, the arena <-> grid passes of the slotted per-bin step
+// (arena_gather_velocities, arena_flush_to_grid), the round-robin walk, the G2P gather from an arena, the tail of G2P
 // (state advance + constitutive update for the next P2G) and the exact gather by hash queries.  No kernel lives here.
 //
 // The transfers replace, behind include/zs_rocm.h:
@@ -79,6 +80,50 @@ template <int SIDE> __device__ __forceinline__ void arena_to_grid(const int (&o)
   const int gx = o[0] + x, gy = o[1] + y, gz = o[2] + z;
   slot = ((gx >= SIDE) << 2) | ((gy >= SIDE) << 1) | (gz >= SIDE);
   cell = ((gx & (SIDE - 1)) * SIDE + (gy & (SIDE - 1))) * SIDE + (gz & (SIDE - 1));
+}
+
+// grid A -> the velocity arena of a bin (6^3 nodes x 3 channels, zero where the node's block is not in the partition); threads 0..215 of
+// the workgroup, one node each.  nbr: [nblocks][8] blocks at offsets {0,1}^3
+template <int SIDE>
+__device__ __forceinline__ void arena_gather_velocities(const BinGeom<SIDE> &geo, const int *nbr, const float *gridA, float *varena, int tid) {
+  using AL = ArenaLds;
+  constexpr int NC = SIDE * SIDE * SIDE;
+  if (tid < 216) {  // node decoded once for the 3 velocity channels
+    const int x = tid / 36, y = (tid / 6) % 6, z = tid % 6;
+    int slot, cell;
+    arena_to_grid<SIDE>(geo.o, x, y, z, slot, cell);
+    const int bn = nbr[(size_t)geo.block * 8 + slot];
+    float *a = varena + AL::at(x, y, z);
+    const float *g = gridA + ((size_t)(bn < 0 ? 0 : bn) * 7 + 1) * NC + cell;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) a[ch * AL::CH] = bn >= 0 ? g[ch * NC] : 0.f;
+  }
+}
+
+// the P2G arena of a bin (6^3 nodes x 7 channels) -> grid B: one global float atomic per non-zero value; threads 0..215.  *lostFlag is
+// set if a node whose block is not in the partition has mass: the partition no longer covers the particles
+template <int SIDE>
+__device__ __forceinline__ void arena_flush_to_grid(const BinGeom<SIDE> &geo, const int *nbr, const float *parena, float *gridB, int *lostFlag,
+                                                    int tid) {
+  using AL = ArenaLds;
+  constexpr int NC = SIDE * SIDE * SIDE;
+  if (tid < 216) {
+    const int x = tid / 36, y = (tid / 6) % 6, z = tid % 6;
+    int slot, cell;
+    arena_to_grid<SIDE>(geo.o, x, y, z, slot, cell);
+    const int bn = nbr[(size_t)geo.block * 8 + slot];
+    const float *a = parena + AL::at(x, y, z);
+    if (bn >= 0) {
+      float *g = gridB + (size_t)bn * 7 * NC + cell;
+#pragma unroll
+      for (int ch = 0; ch < 7; ++ch) {
+        const float v = a[ch * AL::CH];
+        if (v != 0.f) unsafeAtomicAdd(g + ch * NC, v);
+      }
+    } else if (a[0] != 0.f) {
+      *lostFlag = 1;
+    }
+  }
 }
 
 // round-robin walk of one bin: round r visits the r-th particle of every cell (lane) that has one; the lanes

@@ -1,9 +1,9 @@
 #pragma once
 // mpm_fused_common.hpp -- what the fused G2P2G steps on compact storage (mpm_fused_kernels.hpp) and on slotted storage (mpm_slot.hpp)
-// share: the particle record of a fused step, the consumers' channel sets, the staged Q-form record and its accumulation, and the
+// share: the particle record of a fused step, the consumers' channel sets, the staged Q-form record and its accumulation, the
+// accumulators' way into an LDS arena (acc_to_arena), the per-lane stencil-node terms of the list scatters (StencilNodeLane), and the
 // arguments of the compact step's launcher.  No kernel lives here.
-#include "bht.hpp"
-#include "mpm_particles.hpp"
+#include "mpm_arena.hpp"
 
 namespace zsr {
 
@@ -125,6 +125,55 @@ __device__ __forceinline__ void g2p2g_consume_set(const MpmDev &mp, const float 
     }
   }
 }
+
+// The 27 register planes of a consumer lane (lane = cell, acc[k] = its stencil node k) -> the lane's channels of an LDS arena of layout AL;
+// a0 = the cell's stencil node 0 in the first of the NA channels.  The channels belong to this wave alone.  In phase k the 64 lanes of the
+// wave add to 64 distinct nodes; the next phase touches nodes other lanes wrote in this one, so the phases must stay ordered -- but only
+// inside the wave: LDS operations of one wave execute in order, so a wavefront-scope fence (no instruction, it only keeps the compiler from
+// hoisting the next phase's reads over this phase's writes) replaces 27 workgroup barriers.  ZERO: the planes are cleared for the next bin.
+template <class AL, bool ZERO = false, int NA>
+__device__ __forceinline__ void acc_to_arena(float *a0, float (&acc)[27][NA]) {
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    float *g = a0 + AL::at(k / 9, (k / 3) % 3, k % 3);
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+      g[q * AL::CH] += acc[k][q];
+      if constexpr (ZERO) acc[k][q] = 0.f;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  }
+}
+
+// One stencil node (0..26) of a staged record (stage_qform), as the lanes of the list scatters see it (lane = node): only the node's
+// weight formula (alpha + beta (s d0 + t)^2 per axis) and its offset from the centre node are per-lane constants; the channels are a
+// compile-time loop.
+struct StencilNodeLane {
+  int sel[3];
+  float ws[3], wt[3], wa[3], wb[3], oc[3];
+  __device__ __forceinline__ explicit StencilNodeLane(int node) : sel{node / 9, (node / 3) % 3, node % 3} {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      ws[q] = sel[q] == 0 ? -1.f : 1.f;
+      wt[q] = sel[q] == 0 ? 1.5f : (sel[q] == 1 ? -1.f : -0.5f);
+      wa[q] = sel[q] == 1 ? 0.75f : 0.f;
+      wb[q] = sel[q] == 1 ? -1.f : 0.5f;
+      oc[q] = (float)(sel[q] - 1);
+    }
+  }
+  // axis q's factor of the node's weight; d0 = staged local position of that axis
+  __device__ __forceinline__ float weight(int q, float d0) const {
+    const float u = fmaf(ws[q], d0 - floorf(d0 - 0.5f), wt[q]);  // the reference's second base_node (see `edge` in slot_produce_entry)
+    return fmaf(wb[q], u * u, wa[q]);
+  }
+  // what the record at `st` adds to this node in accumulator q of channel set CS; Wt = the node's weight
+  template <int CS> __device__ __forceinline__ float value(const float *st, float Wt, int q) const {
+    using S = ConsumerSet<CS>;
+    if (S::MASS && q == 0) return Wt * st[0];  // mass
+    const float *c = st + (4 + 4 * ((S::STRESS ? 3 : 0) + S::D0 + q - (S::MASS ? 1 : 0))) * 64;
+    return Wt * fmaf(c[192], oc[2], fmaf(c[128], oc[1], fmaf(c[64], oc[0], c[0])));
+  }
+};
 
 // fused G2P2G launch for one block side: defined in mpm_fused_impl.hpp, instantiated in mpm_fused4.hip / mpm_fused8.hip (the
 // 30 instantiations per side of the largest kernel compile in parallel)

@@ -24,8 +24,8 @@ namespace zsr {
 // Particles that are not in the cell they are stored under are exact as before: mis-binned at read -> queue G (global
 // gather + global scatter afterwards); moved out of the cell by this step's advection -> queue P (state stored, global
 // scatter afterwards).
-constexpr int G2P2G_NF = 25;
-constexpr int G2P2G_MQ_CAP = 512;  // in-bin movers a workgroup can take through its LDS queue (a bin holds ~512 particles)  // staged floats per particle: m, x(3), v(3), C(9), P F^T vol(9)
+constexpr int G2P2G_NF = 25;       // staged floats per particle: m, x(3), v(3), C(9), P F^T vol(9)
+constexpr int G2P2G_MQ_CAP = 512;  // in-bin movers a workgroup can take through its LDS queue (a bin holds ~512 particles)
 
 // phase-2 consumer of one staged record.  STRESS = false: mass + momentum (4 channels), true: rhs (3 channels)
 template <bool STRESS>
@@ -224,18 +224,8 @@ __device__ __forceinline__ void g2p2g_body(const MpmDev &mp, const ParticlesDev 
     i0 = i1;
     any = any1;
   }
-  float *a0 = parena + (size_t)(W & 1) * (7 * AL::CH) + AL::at(cx, cy, cz);
-  // Every wave owns its (arena, channel set): waves 0/2 write arena 0 (channels 0-3 / 4-6), waves 1/3 arena 1.  In phase k the 64
-  // lanes of a wave add to 64 distinct nodes; the next phase touches nodes other lanes wrote in this one, so the phases must stay
-  // ordered -- but only inside the wave: LDS operations of one wave execute in order, so a wavefront-scope fence (no instruction,
-  // it only keeps the compiler from hoisting the next phase's reads over this phase's writes) replaces the 27 workgroup barriers.
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    float *g = a0 + AL::at(k / 9, (k / 3) % 3, k % 3);
-#pragma unroll
-    for (int q = 0; q < NCH; ++q) g[((STRESS ? 4 : 0) + q) * AL::CH] += acc[k][q];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  }
+  // every wave owns its (arena, channel set): waves 0/2 write arena 0 (channels 0-3 / 4-6), waves 1/3 arena 1
+  acc_to_arena<AL>(parena + (size_t)(W & 1) * (7 * AL::CH) + (STRESS ? 4 : 0) * AL::CH + AL::at(cx, cy, cz), acc);
   __syncthreads();  // the post-pass and the flush read both arenas
 }
 
@@ -258,6 +248,9 @@ static __global__ __launch_bounds__(256) void g2p2g_reorder_kernel(MpmDev mp, Pa
   if (start == end) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const BinGeom<SIDE> geo(t, bin, mp.kscale);
+  // (The gather below and the flush at the end are spelled out in the two compact kernels although mpm_arena.hpp has them as
+  // arena_gather_velocities / arena_flush_to_grid for the slotted step, and so is the in-bin-mover pass, which has no shared form: as calls
+  // of a common function each of the three changes these kernels' SGPR spill counts -- profiles/fused_dedupe.md.)
   if (tid < 216) {  // node decoded once for the 3 velocity channels
     const int x = tid / 36, y = (tid / 6) % 6, z = tid % 6;
     int slot, cell;
@@ -398,15 +391,7 @@ __device__ __forceinline__ void g2p2g_rs_consumer(const MpmDev &mp, int lane, in
     }
     __syncthreads();
   }
-  // the set's channels of the bin's arena belong to this wave alone; phases ordered inside the wave (see g2p2g_body)
-  float *a0 = parena + (size_t)S::CH0 * AL::CH + AL::at(cx, cy, cz);
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    float *g = a0 + AL::at(k / 9, (k / 3) % 3, k % 3);
-#pragma unroll
-    for (int q = 0; q < S::NA; ++q) g[q * AL::CH] += acc[k][q];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  }
+  acc_to_arena<AL>(parena + (size_t)S::CH0 * AL::CH + AL::at(cx, cy, cz), acc);  // the set's channels of the bin's arena belong to this wave alone
 }
 // producer wave W (0..3): round 4c + W of every chunk c
 template <int SIDE, int SMODEL, int LW, bool WRITE_ALL, int W>

@@ -37,22 +37,20 @@ struct SlotArgs {
 };
 
 constexpr int SL_NCTR = 256, SL_SENT = 8, SL_DELIVERED = 8 + SL_NCTR;  // layout of the status words (zs_rocm.h: ZS_ROCM_SLOT_STATUS_WORDS)
-// bin next to `bin` in direction code (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1), dx, dy, dz in {-1, 0, 1}: same block or the block next to it
-template <int SIDE> __device__ __forceinline__ int neighbour_bin(const int *nbr27, int block, int bin, int code) {
-  if constexpr (SIDE == 4) {
-    return nbr27[(size_t)block * 27 + code];
-  } else {
-    const int dd[3] = {code / 9 - 1, (code / 3) % 3 - 1, code % 3 - 1};
-    const int sub = bin & 7;
-    int sx[3] = {((sub >> 2) & 1) + dd[0], ((sub >> 1) & 1) + dd[1], (sub & 1) + dd[2]}, bo[3];
+// 8^3 blocks: the bin next to bin `sub` (0..7) of block `blk` in direction code (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1), dx, dy, dz in {-1, 0, 1}:
+// a bin of the same block or of the block next to it; row27 = the 27 blocks around `blk` (-1: not in the partition).  (4^3 blocks: bin ==
+// block, the neighbour bin is the neighbour block.)
+__device__ __forceinline__ int neighbour_bin8(const int *row27, int blk, int sub, int code) {
+  if (code == 13) return blk * 8 + sub;
+  const int dd[3] = {code / 9 - 1, (code / 3) % 3 - 1, code % 3 - 1};
+  int sx[3] = {((sub >> 2) & 1) + dd[0], ((sub >> 1) & 1) + dd[1], (sub & 1) + dd[2]}, bo[3];
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      bo[d] = sx[d] < 0 ? -1 : (sx[d] > 1 ? 1 : 0);
-      sx[d] &= 1;
-    }
-    const int nb = nbr27[(size_t)block * 27 + ((bo[0] + 1) * 9 + (bo[1] + 1) * 3 + (bo[2] + 1))];
-    return nb < 0 ? -1 : nb * 8 + ((sx[0] * 2 + sx[1]) * 2 + sx[2]);
+  for (int d = 0; d < 3; ++d) {
+    bo[d] = sx[d] < 0 ? -1 : (sx[d] > 1 ? 1 : 0);
+    sx[d] &= 1;
   }
+  const int nb = row27[(bo[0] + 1) * 9 + (bo[1] + 1) * 3 + (bo[2] + 1)];
+  return nb < 0 ? -1 : nb * 8 + ((sx[0] * 2 + sx[1]) * 2 + sx[2]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ main kernel
@@ -182,8 +180,7 @@ __device__ __forceinline__ void outbox_scatter_global(const MpmDev &mp, const GE
 
 // Movers whose new cell is not a lane of this bin (or whose cell's arrival queue was full), and stayers whose local position rounded
 // onto 1.5: the channels of set CS of their 27 node terms straight to the grid.  Two list entries per pass: lane = (entry parity,
-// stencil node); the channels of the set are a compile-time loop, so only the node's weight formula (alpha + beta (s d0 + t)^2 per
-// axis) and its offset from the centre node are per-lane constants.  Staged record: stage_qform.
+// stencil node, StencilNodeLane).  Staged record: stage_qform.
 template <int SIDE, int CS, class GEO>
 __device__ __forceinline__ void slot_xlist_scatter(const MpmDev &mp, const GEO &geo, const float *stage, const unsigned *xq, int nx, int lane,
                                                    const int *nbrBlk, const SlotArgs &A) {
@@ -191,16 +188,7 @@ __device__ __forceinline__ void slot_xlist_scatter(const MpmDev &mp, const GEO &
   constexpr int NC = SIDE * SIDE * SIDE;
   const int node = lane & 31, half = lane >> 5;
   if (node >= 27 || nx <= 0) return;
-  const int sel[3] = {node / 9, (node / 3) % 3, node % 3};
-  float ws[3], wt[3], wa[3], wb[3], oc[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    ws[q] = sel[q] == 0 ? -1.f : 1.f;
-    wt[q] = sel[q] == 0 ? 1.5f : (sel[q] == 1 ? -1.f : -0.5f);
-    wa[q] = sel[q] == 1 ? 0.75f : 0.f;
-    wb[q] = sel[q] == 1 ? -1.f : 0.5f;
-    oc[q] = (float)(sel[q] - 1);
-  }
+  const StencilNodeLane sn(node);
 #pragma unroll 1
   for (int k = half; k < nx; k += 2) {
     const unsigned e = xq[k];
@@ -209,10 +197,8 @@ __device__ __forceinline__ void slot_xlist_scatter(const MpmDev &mp, const GEO &
     int g[3], code = 0;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      const float d0 = st[(1 + q) * 64];
-      const float u = fmaf(ws[q], d0 - floorf(d0 - 0.5f), wt[q]);  // the reference's second base_node (see `edge` in the producer)
-      Wt *= fmaf(wb[q], u * u, wa[q]);
-      g[q] = (int)((e >> (10 + 3 * q)) & 7u) - 1 + geo.o[q] + sel[q];
+      Wt *= sn.weight(q, st[(1 + q) * 64]);
+      g[q] = (int)((e >> (10 + 3 * q)) & 7u) - 1 + geo.o[q] + sn.sel[q];
       code = code * 3 + 1 + (g[q] >= SIDE ? 1 : 0) - (g[q] < 0 ? 1 : 0);
     }
     const int bn = nbrBlk[code];
@@ -221,13 +207,7 @@ __device__ __forceinline__ void slot_xlist_scatter(const MpmDev &mp, const GEO &
       float *gp = A.gridB + ((size_t)bn * 7 + S::CH0) * NC + cell;
 #pragma unroll
       for (int q = 0; q < S::NA; ++q) {
-        float val;
-        if (S::MASS && q == 0) {
-          val = Wt * st[0];  // mass
-        } else {
-          const float *c = st + (4 + 4 * ((S::STRESS ? 3 : 0) + S::D0 + q - (S::MASS ? 1 : 0))) * 64;
-          val = Wt * fmaf(c[192], oc[2], fmaf(c[128], oc[1], fmaf(c[64], oc[0], c[0])));
-        }
+        const float val = sn.value<CS>(st, Wt, q);
         if (val != 0.f) unsafeAtomicAdd(gp + q * NC, val);
       }
     } else if (S::MASS) {
@@ -479,25 +459,18 @@ __device__ __forceinline__ bool slot_produce_entry(const MpmDev &mp, const Parti
 template <int SIDE, int SMODEL, bool WRITE_ALL, int W>
 __device__ __forceinline__ void g2p2g_slot_producer(const MpmDev &mp, const ParticlesDev &ps, const BinGeom<SIDE> &geo, int bin, int total,
                                                     int lane, int nchunks, const SlotShared &sh, const SlotArgs &A) {
-  using AL = ArenaLds;
   constexpr int LW = 64;
   constexpr bool DP = model_uses_logjp(SMODEL);
   constexpr bool FLUID = model_is_fluid(SMODEL);
-  constexpr int NC = SIDE * SIDE * SIDE;
-  const float dxi = mp.dxi;
-  const float D_inv = mp.D_inv;
   const size_t rowBase = (size_t)bin * (size_t)A.K;
   const unsigned kmask = A.K >= 32 ? 0xffffffffu : ((1u << A.K) - 1u);
   float *const varena = sh.varena, *const stage = sh.stage;
   unsigned long long *const smask = sh.smask;
   const unsigned short *const tab = sh.tab;
-  unsigned *const mask0 = sh.mask0, *const clr = sh.clr, *const arrLocal = sh.arrLocal;
-  const int *const nbrBin = sh.nbrBin;
   unsigned(*const arrCnt)[64] = sh.arrCnt;
   unsigned short(*const arrQ)[64][SL_ARRQ] = sh.arrQ;
   unsigned *const xCnt = sh.xCnt;
   unsigned(*const xq)[SL_XQ] = sh.xq;
-  int *const outCount = sh.outCount, *const sent = sh.sent, *const homed = sh.homed, *const xOver = sh.xOver;
   const SlotBinView bv{bin, {geo.org[0], geo.org[1], geo.org[2]}, rowBase, kmask, sh.varena, sh.mask0, sh.clr, sh.arrLocal, sh.nbrBin,
                        sh.outCount, sh.sent, sh.homed, sh.xOver, nullptr, nullptr};
   RecG<LW, DP, FLUID> cur, nxt;
@@ -516,19 +489,7 @@ __device__ __forceinline__ void g2p2g_slot_producer(const MpmDev &mp, const Part
       nxt.load(ps, i1);
     }
   }
-  {
-    const int tid = (int)threadIdx.x;  // the four producer waves are threads 0..255
-    if (tid < 216) {
-      const int x = tid / 36, y = (tid / 6) % 6, z = tid % 6;
-      int slot, cell;
-      arena_to_grid<SIDE>(geo.o, x, y, z, slot, cell);
-      const int bn = A.nbr[(size_t)geo.block * 8 + slot];
-      float *a = varena + AL::at(x, y, z);
-      const float *g = A.gridA + ((size_t)(bn < 0 ? 0 : bn) * 7 + 1) * NC + cell;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) a[ch * AL::CH] = bn >= 0 ? g[ch * NC] : 0.f;
-    }
-  }
+  arena_gather_velocities<SIDE>(geo, A.nbr, A.gridA, varena, (int)threadIdx.x);  // the four producer waves are threads 0..255
   __syncthreads();
   for (int it = 0; it < nchunks; ++it) {
     {
@@ -638,18 +599,11 @@ __device__ __forceinline__ void g2p2g_slot_consumer(const MpmDev &mp, const BinG
     }
     __syncthreads();
   }
-  // the set's channels of the bin's arena belong to this wave alone; phases ordered inside the wave (see g2p2g_body)
+  // the set's channels of the bin's arena belong to this wave alone
   // (the arena lives in the staging ring, which nobody reads after the loop's last barrier: cleared here, by the wave that owns the channels)
   for (int k = lane; k < S::NA * AL::CH; k += 64) parena[(size_t)S::CH0 * AL::CH + k] = 0.f;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  float *a0 = parena + (size_t)S::CH0 * AL::CH + AL::at(cx, cy, cz);
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    float *g = a0 + AL::at(k / 9, (k / 3) % 3, k % 3);
-#pragma unroll
-    for (int q = 0; q < S::NA; ++q) g[q * AL::CH] += acc[k][q];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  }
+  acc_to_arena<AL>(parena + (size_t)S::CH0 * AL::CH + AL::at(cx, cy, cz), acc);
 }
 
 // mpm_slotblk.hip: the step's main kernel for 8^3 blocks, one workgroup per block (blocks [A.binBase / 8, + A.nbins / 8))

@@ -62,9 +62,7 @@ struct BlkShared {
   unsigned (*xq)[SL_XQ];                     // [3]
   int *nbrBlk, (*nbrBin)[27], *nbr8;
   int (*cnt)[4];                             // [2]: outCount, sent, homed, xOver of the bin of that parity
-  int *total, *gbase, *nch, *binQ, *oc;      // [8] per bin: occupied slots, first chunk number, chunks, position among the block's non-empty bins,
-                                             // outbox records (after the bin has been finished)
-  unsigned char *chBin, *chIdx;              // [SB_MAXCH] chunk -> bin of the block, chunk number inside the bin
+  int *oc;                                   // [8] per bin: outbox records (after the bin has been finished)
   const unsigned *desc;                      // [SB_MAXCH + 5] desc[g + 1] = packed descriptor of chunk g (ChunkDesc), zero outside [0, G)
   unsigned *done;                            // consumer waves x chunks consumed
   int *sums;                                 // [0] sent, [1] homed, [2] bins whose outbox holds records that still have to be scattered
@@ -105,19 +103,6 @@ __device__ __forceinline__ void blk_build_tab(unsigned mask, int lane, int w, in
     total += __popcll(occ);
   }
 }
-// the 27 bins around bin b of this block (direction code (dx + 1) 9 + (dy + 1) 3 + dz + 1), from the block's 27 neighbour blocks
-__device__ __forceinline__ int blk_neighbour_bin(const int *nbrBlk, int blk, int b, int code) {
-  if (code == 13) return blk * 8 + b;
-  const int dd[3] = {code / 9 - 1, (code / 3) % 3 - 1, code % 3 - 1};
-  int sx[3] = {((b >> 2) & 1) + dd[0], ((b >> 1) & 1) + dd[1], (b & 1) + dd[2]}, bo[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    bo[d] = sx[d] < 0 ? -1 : (sx[d] > 1 ? 1 : 0);
-    sx[d] &= 1;
-  }
-  const int nb = nbrBlk[(bo[0] + 1) * 9 + (bo[1] + 1) * 3 + (bo[2] + 1)];
-  return nb < 0 ? -1 : nb * 8 + ((sx[0] * 2 + sx[1]) * 2 + sx[2]);
-}
 
 // a finished bin (all of its chunks produced by all producer waves): departures of its cells for slot_rehome_kernel / slot_commit_kernel,
 // its outbox count; the parity's counters are zero again (its arrivals can still grow: the kernel writes them after its last barrier).  One wave, lane = cell; every LDS read is issued before the
@@ -156,23 +141,14 @@ struct ArenaBin8 {
 // The chunk's list (movers into neighbour bins, arrival-queue overflow, stayers whose local position rounded onto 1.5): the channels of
 // set CS of their 27 node terms into the bin's 8^3 arena `pa` (this wave's channels).  Two list entries per pass, lane = (entry parity,
 // stencil node); the two entries of a pass may share nodes, so the halves do their read-add-write one after the other (LDS operations of
-// a wave execute in order).  Weights and staged record as slot_xlist_scatter.
+// a wave execute in order).  Weights and values: StencilNodeLane, as slot_xlist_scatter.
 template <int CS>
 __device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned *xq, int nx, int lane, float *pa) {
   using S = ConsumerSet<CS>;
   using A8 = ArenaBin8;
   const int node = lane & 31, half = lane >> 5;
   if (nx <= 0) return;
-  const int sel[3] = {node / 9, (node / 3) % 3, node % 3};
-  float ws[3], wt[3], wa[3], wb[3], oc[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    ws[q] = sel[q] == 0 ? -1.f : 1.f;
-    wt[q] = sel[q] == 0 ? 1.5f : (sel[q] == 1 ? -1.f : -0.5f);
-    wa[q] = sel[q] == 1 ? 0.75f : 0.f;
-    wb[q] = sel[q] == 1 ? -1.f : 0.5f;
-    oc[q] = (float)(sel[q] - 1);
-  }
+  const StencilNodeLane sn(node);
 #pragma unroll 1
   for (int k0 = 0; k0 < nx; k0 += 2) {
     const int k = k0 + half;
@@ -184,22 +160,11 @@ __device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned
       const float *st = stage + (size_t)((e & 1023u) >> 6) * (G2P2G_QF * 64) + (e & 63u);
       float Wt = 1.f;
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const float d0 = st[(1 + q) * 64];
-        const float u = fmaf(ws[q], d0 - floorf(d0 - 0.5f), wt[q]);  // the reference's second base_node (see `edge` in the producer)
-        Wt *= fmaf(wb[q], u * u, wa[q]);
-      }
+      for (int q = 0; q < 3; ++q) Wt *= sn.weight(q, st[(1 + q) * 64]);
       // (the entry carries new cell + 1 per axis = the arena coordinate of the stencil's node 0)
-      an = A8::at((int)((e >> 10) & 7u) + sel[0], (int)((e >> 13) & 7u) + sel[1], (int)((e >> 16) & 7u) + sel[2]);
+      an = A8::at((int)((e >> 10) & 7u) + sn.sel[0], (int)((e >> 13) & 7u) + sn.sel[1], (int)((e >> 16) & 7u) + sn.sel[2]);
 #pragma unroll
-      for (int q = 0; q < S::NA; ++q) {
-        if (S::MASS && q == 0) {
-          val[q] = Wt * st[0];  // mass
-        } else {
-          const float *c = st + (4 + 4 * ((S::STRESS ? 3 : 0) + S::D0 + q - (S::MASS ? 1 : 0))) * 64;
-          val[q] = Wt * fmaf(c[192], oc[2], fmaf(c[128], oc[1], fmaf(c[64], oc[0], c[0])));
-        }
-      }
+      for (int q = 0; q < S::NA; ++q) val[q] = sn.value<CS>(st, Wt, q);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -314,7 +279,7 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
   // The kernel head has done the bins that start with chunks 0 and 1; the one that starts with chunk 2 is "iteration -1", here.
   auto binState = [&](int g, const ChunkDesc &c2, const ChunkDesc &c3) {  // c2 / c3: chunks g + 2 / g + 3
     if (g + 3 < G && c3.idx() == 0) blk_build_tab(sh.masks[c3.bin()][lane], lane, CS, 4, sh.tab[c3.qp()]);
-    if (CS == 2 && g >= 0 && g + 2 < G && c2.idx() == 0 && lane < 27) sh.nbrBin[c2.qp()][lane] = blk_neighbour_bin(sh.nbrBlk, blk, c2.bin(), lane);
+    if (CS == 2 && g >= 0 && g + 2 < G && c2.idx() == 0 && lane < 27) sh.nbrBin[c2.qp()][lane] = neighbour_bin8(sh.nbrBlk, blk, c2.bin(), lane);
   };
   {
     ChunkDesc d[5];
@@ -381,17 +346,7 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
     if (d[1].last()) {
       // last chunk of the bin: the set's channels of the bin's arena belong to this wave alone -- add the 27 register planes on top of
       // the lists' terms (phases ordered inside the wave), send the arena's nodes to the grid; no other wave is involved
-      float *a0 = pa + AL::at(cx + 1, cy + 1, cz + 1);
-#pragma unroll
-      for (int k = 0; k < 27; ++k) {
-        float *gp = a0 + AL::at(k / 9, (k / 3) % 3, k % 3);
-#pragma unroll
-        for (int q = 0; q < S::NA; ++q) {
-          gp[q * AL::CH] += acc[k][q];
-          acc[k][q] = 0.f;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      }
+      acc_to_arena<AL, true>(pa + AL::at(cx + 1, cy + 1, cz + 1), acc);
       const SubGeom sg = sub_geom(borg, b);
       for (int n = lane; n < 512; n += 64) {
         const int x = n >> 6, y = (n >> 3) & 7, z = n & 7;
@@ -436,7 +391,7 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   __shared__ unsigned s_done;
   __shared__ int s_sums[3], s_G;
   const BlkShared sh{s_varena, s_parena, s_stage, s_smask, s_tab, s_masks, s_clr, s_arrLocal, s_arrCnt, s_arrQ, s_xCnt, s_xq, s_nbrBlk, s_nbrBin, s_nbr8,
-                     s_cnt, s_total, s_gbase, s_nch, s_binQ, s_oc, s_chBin, s_chIdx, s_desc, &s_done, s_sums};
+                     s_cnt, s_oc, s_desc, &s_done, s_sums};
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int blk = (int)blockIdx.x + A.binBase / 8;
   const int bin0 = blk * 8;
@@ -510,11 +465,11 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   {  // entry tables and neighbour bins of the bins of chunks 0 and 1 (all eight waves; later ones: the producers, two chunks ahead)
     const int b0 = s_chBin[0];
     blk_build_tab(s_masks[b0][lane], lane, w, 8, s_tab[s_binQ[b0] & 1]);
-    if (tid < 27) s_nbrBin[s_binQ[b0] & 1][tid] = blk_neighbour_bin(s_nbrBlk, blk, b0, tid);
+    if (tid < 27) s_nbrBin[s_binQ[b0] & 1][tid] = neighbour_bin8(s_nbrBlk, blk, b0, tid);
     if (G > 1 && s_chIdx[1] == 0) {
       const int b1 = s_chBin[1];
       blk_build_tab(s_masks[b1][lane], lane, w, 8, s_tab[s_binQ[b1] & 1]);
-      if (tid >= 64 && tid < 64 + 27) s_nbrBin[s_binQ[b1] & 1][tid - 64] = blk_neighbour_bin(s_nbrBlk, blk, b1, tid - 64);
+      if (tid >= 64 && tid < 64 + 27) s_nbrBin[s_binQ[b1] & 1][tid - 64] = neighbour_bin8(s_nbrBlk, blk, b1, tid - 64);
     }
   }
   __syncthreads();
@@ -572,19 +527,13 @@ template <int M, bool WA> static void launch_blk(hipStream_t stream, unsigned nb
 void launch_g2p2g_slotblk(hipStream_t stream, int model, bool writeAll, const MpmDev &mp, const ParticlesDev &pd, const BhtDev &t, const SlotArgs &A) {
   const unsigned nblk = (unsigned)(A.nbins / 8);
   if (!nblk) return;
-#define ZSR_BLK(M)                                        \
-  case M:                                                 \
+#define CALL_BLK(SS, M)                                            \
+  do {                                                             \
     if (writeAll) launch_blk<M, true>(stream, nblk, mp, pd, t, A); \
     else launch_blk<M, false>(stream, nblk, mp, pd, t, A);         \
-    break;
-  switch (model) {
-    ZSR_BLK(ZS_MPM_FIXED_COROTATED)
-    ZSR_BLK(ZS_MPM_DRUCKER_PRAGER)
-    ZSR_BLK(ZS_MPM_VONMISES_FIXED_COROTATED)
-    ZSR_BLK(ZS_MPM_NACC)
-    ZSR_BLK(ZS_MPM_EQUATION_OF_STATE)
-  }
-#undef ZSR_BLK
+  } while (0)
+  ZSR_DISPATCH_PURE_(8, model, CALL_BLK)  // (the caller has rejected anything that is not one of the five models)
+#undef CALL_BLK
 }
 
 }  // namespace zsr

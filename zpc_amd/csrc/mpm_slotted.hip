@@ -124,7 +124,7 @@ static __global__ __launch_bounds__(256) void partition_edge_kernel(BhtDev t, in
 template <int SIDE, int SMODEL, bool WRITE_ALL>
 static __global__ __launch_bounds__(512, 4) void g2p2g_slot_kernel(MpmDev mp, ParticlesDev ps, BhtDev t, SlotArgs A) {
   using AL = ArenaLds;
-  constexpr int NC = SIDE * SIDE * SIDE;
+  static_assert(SIDE == 4, "one workgroup per bin serves 4^3 blocks (bin == block); 8^3 blocks run g2p2g_slotblk_kernel");
   __shared__ float s_varena[3 * AL::CH];
   __shared__ float s_stage[SL_NG * G2P2G_QF * 64];
   float *const s_parena = s_stage;  // the bin's P2G arena (7 * AL::CH floats) is filled after the last chunk has been consumed: it shares the ring
@@ -174,8 +174,9 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slot_kernel(MpmDev mp, Pa
   if (tid == 0 && A.blockEdge && A.blockEdge[geo.block]) A.status[3] = 1;
   if (tid >= 64 && tid < 64 + 27) {
     const int code = tid - 64;
-    s_nbrBlk[code] = A.nbr27[(size_t)geo.block * 27 + code];
-    s_nbrBin[code] = code == 13 ? bin : neighbour_bin<SIDE>(A.nbr27, geo.block, bin, code);
+    const int nb = A.nbr27[(size_t)geo.block * 27 + code];
+    s_nbrBlk[code] = nb;
+    s_nbrBin[code] = code == 13 ? bin : nb;  // bin == block: the neighbour bin is the neighbour block
   }
   __syncthreads();  // the table is complete
   if (w == 0) g2p2g_slot_producer<SIDE, SMODEL, WRITE_ALL, 0>(mp, ps, geo, bin, total, lane, nchunks, sh, A);
@@ -201,23 +202,7 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slot_kernel(MpmDev mp, Pa
     if (s_sent) atomicAdd(&A.status[SL_SENT + (bin & (SL_NCTR - 1))], s_sent);
     if (s_homed) atomicAdd(&A.status[SL_DELIVERED + (bin & (SL_NCTR - 1))], s_homed);
   }
-  if (tid < 216) {
-    const int x = tid / 36, y = (tid / 6) % 6, z = tid % 6;
-    int slot, cell;
-    arena_to_grid<SIDE>(geo.o, x, y, z, slot, cell);
-    const int bn = A.nbr[(size_t)geo.block * 8 + slot];
-    const float *a = s_parena + AL::at(x, y, z);
-    if (bn >= 0) {
-      float *g = A.gridB + (size_t)bn * 7 * NC + cell;
-#pragma unroll
-      for (int ch = 0; ch < 7; ++ch) {
-        const float v = a[ch * AL::CH];
-        if (v != 0.f) unsafeAtomicAdd(g + ch * NC, v);
-      }
-    } else if (a[0] != 0.f) {
-      A.status[2] = 1;  // mass for a node whose block is not in the partition
-    }
-  }
+  arena_flush_to_grid<SIDE>(geo, A.nbr, s_parena, A.gridB, &A.status[2], tid);
   if (s_xOver > 0) {  // (rare) a chunk had more than SL_XQ movers for the consumers' list: their full records -> grid, all eight waves
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's record stores have reached L2 ...
     __syncthreads();                                    // ... and so have everybody else's (and the arena, which shares the ring, has been flushed)
