@@ -10,6 +10,7 @@
 // entry (one hash query per block change), the staged block kernels (zpc_amd/csrc/levelset.hip: values from LDS) and the C++ face form
 // the same sums in the same order and give the same bits.  The normal is a float finite difference: compile translation units that use
 // this header with -ffp-contract=off, like collider_device.hpp.
+// Below the single level set: TransitionLevelSetView, the blend of two of them at a phase between two keyframes, and its collider.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -145,6 +146,116 @@ struct LevelSetColliderDev {
   }
   __device__ __forceinline__ bool resolveCollision(const float (&x)[3], float (&v)[3], float erosion = 0.f) const {
     return resolveCollision(LevelSetDirectFetch(ls), x, v, erosion);
+  }
+};
+
+// ---- keyframed level sets: the blend of two level sets `src` and `dst` a keyframe spacing stepDt apart, at the phase alpha in [0, 1]
+// between them (the reference's TransitionLevelSetView over the two front entries of a keyframe queue, geometry/LevelSet.h).  At a point
+// x of level-set world space every call first moves x along the mean material velocity, back to the time of src and on to the time of dst:
+//   vs  = src.getMaterialVelocity(x)        vd = dst.getMaterialVelocity(x)        (0 for a level set without "v")
+//   v_d = (vs_d + vd_d) * 0.5f
+//   a0  = alpha * stepDt                    a1 = (1.f - alpha) * stepDt
+//   x0_d = x_d - a0 * v_d                   x1_d = x_d + a1 * v_d
+// and then blends the two level sets' own answers, component by component:
+//   getSignedDistance(x)   = (1.f - alpha) * src.getSignedDistance(x0)   + alpha * dst.getSignedDistance(x1)
+//   getNormal(x)           = (1.f - alpha) * src.getNormal(x0)           + alpha * dst.getNormal(x1)              (not renormalised)
+//   getMaterialVelocity(x) = (1.f - alpha) * src.getMaterialVelocity(x0) + alpha * dst.getMaterialVelocity(x1)
+// Every line is ONE float32 operation per operator as written, left to right, without contraction: the tests reproduce the chain up to
+// x0 and x1 in numpy float32 (tests/ref64_transition.py), so every path -- the per-point entries, the staged block kernels, the C++
+// face -- keeps this order.  Each level set reads its cells through its own fetch functor.  Where a level set's gradient vanishes (a
+// stencil of equal values, as beyond its band) its normal is 0 / 0 and so is the blend, as in the reference: keep stepDt * speed inside
+// the band (zpc_amd.levelset.LevelSetSequence.push checks it).
+struct TransitionLevelSetView {
+  LevelSetView src, dst;
+  float stepDt, alpha;
+  __host__ __device__ TransitionLevelSetView() = default;
+  __host__ __device__ TransitionLevelSetView(const zs_rocm_levelset_transition &t) : src(t.src), dst(t.dst), stepDt(t.stepDt), alpha(t.alpha) {}
+
+  __host__ __device__ __forceinline__ bool has_velocity() const { return src.velChannel >= 0 || dst.velChannel >= 0; }
+  // the two displaced sample points of x
+  template <class FS, class FD>
+  __device__ __forceinline__ void displaced(const FS &fs, const FD &fd, const float (&x)[3], float (&x0)[3], float (&x1)[3]) const {
+    float vs[3], vd[3];
+    src.getMaterialVelocity(fs, x, vs);
+    dst.getMaterialVelocity(fd, x, vd);
+    const float a0 = alpha * stepDt, a1 = (1.f - alpha) * stepDt;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float v = (vs[d] + vd[d]) * 0.5f;
+      x0[d] = x[d] - a0 * v;
+      x1[d] = x[d] + a1 * v;
+    }
+  }
+  // the blends at displaced points already formed
+  template <class FS, class FD> __device__ __forceinline__ float sdf_at(const FS &fs, const FD &fd, const float (&x0)[3], const float (&x1)[3]) const {
+    return (1.f - alpha) * src.getSignedDistance(fs, x0) + alpha * dst.getSignedDistance(fd, x1);
+  }
+  template <class FS, class FD>
+  __device__ __forceinline__ void normal_at(const FS &fs, const FD &fd, const float (&x0)[3], const float (&x1)[3], float (&n)[3]) const {
+    float ns[3], nd[3];
+    src.getNormal(fs, x0, ns);
+    dst.getNormal(fd, x1, nd);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) n[d] = (1.f - alpha) * ns[d] + alpha * nd[d];
+  }
+  // false (and vm = 0) when neither level set has "v"
+  template <class FS, class FD>
+  __device__ __forceinline__ bool velocity_at(const FS &fs, const FD &fd, const float (&x0)[3], const float (&x1)[3], float (&vm)[3]) const {
+    float vs[3], vd[3];
+    src.getMaterialVelocity(fs, x0, vs);
+    dst.getMaterialVelocity(fd, x1, vd);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) vm[d] = (1.f - alpha) * vs[d] + alpha * vd[d];
+    return has_velocity();
+  }
+  template <class FS, class FD> __device__ __forceinline__ float getSignedDistance(const FS &fs, const FD &fd, const float (&x)[3]) const {
+    float x0[3], x1[3];
+    displaced(fs, fd, x, x0, x1);
+    return sdf_at(fs, fd, x0, x1);
+  }
+  template <class FS, class FD> __device__ __forceinline__ void getNormal(const FS &fs, const FD &fd, const float (&x)[3], float (&n)[3]) const {
+    float x0[3], x1[3];
+    displaced(fs, fd, x, x0, x1);
+    normal_at(fs, fd, x0, x1, n);
+  }
+  template <class FS, class FD>
+  __device__ __forceinline__ bool getMaterialVelocity(const FS &fs, const FD &fd, const float (&x)[3], float (&vm)[3]) const {
+    float x0[3], x1[3];
+    displaced(fs, fd, x, x0, x1);
+    return velocity_at(fs, fd, x0, x1, vm);
+  }
+};
+
+// the transition as the shape of ColliderDev::resolve_with.  The three calls of one resolveCollision come at the same X: the displaced
+// points are formed at the first and kept (the same operations on the same inputs, so the same bits as forming them three times).
+template <class FS, class FD> struct TransitionShape {
+  const TransitionLevelSetView &tr;
+  const FS &fs;
+  const FD &fd;
+  mutable float at[3], x0[3], x1[3];
+  mutable bool have;
+  __device__ __forceinline__ TransitionShape(const TransitionLevelSetView &t, const FS &s, const FD &d) : tr(t), fs(s), fd(d), have(false) {}
+  __device__ __forceinline__ void move_to(const float (&X)[3]) const {
+    if (have && X[0] == at[0] && X[1] == at[1] && X[2] == at[2]) return;
+    tr.displaced(fs, fd, X, x0, x1);
+    at[0] = X[0]; at[1] = X[1]; at[2] = X[2];
+    have = true;
+  }
+  __device__ __forceinline__ float signed_distance(const float (&X)[3]) const { move_to(X); return tr.sdf_at(fs, fd, x0, x1); }
+  __device__ __forceinline__ void normal(const float (&X)[3], float (&n)[3]) const { move_to(X); tr.normal_at(fs, fd, x0, x1, n); }
+  __device__ __forceinline__ bool material_velocity(const float (&X)[3], float (&vm)[3]) const { move_to(X); return tr.velocity_at(fs, fd, x0, x1, vm); }
+};
+
+// Collider over the transition: type and motion of a zs_rocm_collider around the blended level set
+struct TransitionColliderDev {
+  ColliderDev motion;
+  TransitionLevelSetView tr;
+  template <class FS, class FD>
+  __device__ __forceinline__ bool resolveCollision(const FS &fs, const FD &fd, const float (&x)[3], float (&v)[3], float erosion = 0.f) const {
+    return motion.resolve_with(TransitionShape<FS, FD>(tr, fs, fd), x, v, erosion);
+  }
+  __device__ __forceinline__ bool resolveCollision(const float (&x)[3], float (&v)[3], float erosion = 0.f) const {
+    return resolveCollision(LevelSetDirectFetch(tr.src), LevelSetDirectFetch(tr.dst), x, v, erosion);
   }
 };
 

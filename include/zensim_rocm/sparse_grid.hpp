@@ -445,6 +445,20 @@ template <int dim_, class T, int Side> struct SparseGridView {
 // zs::Collider<LS> (geometry/Collider.h:10-110) over a level-set view: `Collider{view, collider_e::Slip}.resolveCollision(x, v)` inside
 // a kernel.  Identity transform unless the members are set (setTranslation / setRotation of the reference are plain members here).
 enum struct collider_e : int { Sticky = 0, Slip = 1, Separate = 2 };  // geometry/Collider.h:8
+namespace detail {
+// type and motion of a Collider<...> as the C ABI's struct (geometry and param are not read by the level-set colliders)
+template <class C> __host__ __device__ __forceinline__ zsr::ColliderDev collider_motion(const C &col) {
+  zsr::ColliderDev m;
+  m.geometry = 0;
+  m.type = (int)col.type;
+  for (int i = 0; i < 8; ++i) m.param[i] = 0.f;
+  m.s = col.s;
+  m.dsdt = col.dsdt;
+  for (int i = 0; i < 9; ++i) m.R[i] = col.R[i];
+  for (int i = 0; i < 3; ++i) { m.omega[i] = col.omega[i]; m.b[i] = col.b[i]; m.dbdt[i] = col.dbdt[i]; }
+  return m;
+}
+}  // namespace detail
 template <class LS> struct Collider {
   using TV = small_vec<float, 3>;
   LS levelset;
@@ -454,13 +468,7 @@ template <class LS> struct Collider {
   float omega[3] = {0.f, 0.f, 0.f}, b[3] = {0.f, 0.f, 0.f}, dbdt[3] = {0.f, 0.f, 0.f};
   __device__ __forceinline__ zsr::LevelSetColliderDev dev() const {
     zsr::LevelSetColliderDev c;
-    c.motion.geometry = 0;
-    c.motion.type = (int)type;
-    for (int i = 0; i < 8; ++i) c.motion.param[i] = 0.f;
-    c.motion.s = s;
-    c.motion.dsdt = dsdt;
-    for (int i = 0; i < 9; ++i) c.motion.R[i] = R[i];
-    for (int i = 0; i < 3; ++i) { c.motion.omega[i] = omega[i]; c.motion.b[i] = b[i]; c.motion.dbdt[i] = dbdt[i]; }
+    c.motion = detail::collider_motion(*this);
     c.ls = levelset.levelSetView();
     return c;
   }
@@ -469,6 +477,63 @@ template <class LS> struct Collider {
     float xmb[3], X[3];
     c.motion.to_material(x.v, xmb, X);
     return c.ls.getSignedDistance(zsr::LevelSetDirectFetch(c.ls), X) < 0.f;
+  }
+  __device__ __forceinline__ bool resolveCollision(const TV &x, TV &v, float erosion = 0.f) const { return dev().resolveCollision(x.v, v.v, erosion); }
+};
+
+// TransitionLevelSetView (geometry/LevelSet.h) over two level-set views of the same type: the blend of `src` and `dst`, a keyframe
+// spacing stepDt apart, at the phase alpha.  `TransitionLevelSetView{viewA, viewB, stepDt, alpha}` inside a kernel, on its own or as the
+// level set of a Collider.  The arithmetic is zsr::TransitionLevelSetView's (levelset_device.hpp): the bits of the C ABI's transition
+// entries; build the translation unit with -ffp-contract=off.
+template <class LS> struct TransitionLevelSetView {
+  using TV = small_vec<float, 3>;
+  LS src, dst;
+  float stepDt = 0.f, alpha = 0.f;
+  ZS_FUNCTION zsr::TransitionLevelSetView transitionView() const {
+    zsr::TransitionLevelSetView t;
+    t.src = src.levelSetView();
+    t.dst = dst.levelSetView();
+    t.stepDt = stepDt;
+    t.alpha = alpha;
+    return t;
+  }
+  __device__ __forceinline__ float getSignedDistance(const TV &x) const {
+    const zsr::TransitionLevelSetView t = transitionView();
+    return t.getSignedDistance(zsr::LevelSetDirectFetch(t.src), zsr::LevelSetDirectFetch(t.dst), x.v);
+  }
+  __device__ __forceinline__ TV getNormal(const TV &x) const {
+    const zsr::TransitionLevelSetView t = transitionView();
+    TV n;
+    t.getNormal(zsr::LevelSetDirectFetch(t.src), zsr::LevelSetDirectFetch(t.dst), x.v, n.v);
+    return n;
+  }
+  __device__ __forceinline__ TV getMaterialVelocity(const TV &x) const {
+    const zsr::TransitionLevelSetView t = transitionView();
+    TV vm;
+    t.getMaterialVelocity(zsr::LevelSetDirectFetch(t.src), zsr::LevelSetDirectFetch(t.dst), x.v, vm.v);
+    return vm;
+  }
+};
+template <class LS> TransitionLevelSetView(LS, LS, float, float) -> TransitionLevelSetView<LS>;
+
+template <class LS> struct Collider<TransitionLevelSetView<LS>> {
+  using TV = small_vec<float, 3>;
+  TransitionLevelSetView<LS> levelset;
+  collider_e type = collider_e::Sticky;
+  float s = 1.f, dsdt = 0.f;
+  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};  // row-major
+  float omega[3] = {0.f, 0.f, 0.f}, b[3] = {0.f, 0.f, 0.f}, dbdt[3] = {0.f, 0.f, 0.f};
+  __device__ __forceinline__ zsr::TransitionColliderDev dev() const {
+    zsr::TransitionColliderDev c;
+    c.motion = detail::collider_motion(*this);
+    c.tr = levelset.transitionView();
+    return c;
+  }
+  __device__ __forceinline__ bool queryInside(const TV &x) const {
+    const zsr::TransitionColliderDev c = dev();
+    float xmb[3], X[3];
+    c.motion.to_material(x.v, xmb, X);
+    return c.tr.getSignedDistance(zsr::LevelSetDirectFetch(c.tr.src), zsr::LevelSetDirectFetch(c.tr.dst), X) < 0.f;
   }
   __device__ __forceinline__ bool resolveCollision(const TV &x, TV &v, float erosion = 0.f) const { return dev().resolveCollision(x.v, v.v, erosion); }
 };

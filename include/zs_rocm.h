@@ -732,6 +732,49 @@ ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_solve_levelset(zs_rocm_policy *, const z
                                                        const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount,
                                                        const int *nbr, const zs_rocm_collider *collider, const zs_rocm_levelset *,
                                                        const float *b, float *x, int maxIters, float tol, float relTol, int *iters);
+/* ---- keyframed level-set colliders (include/zensim_rocm/levelset_device.hpp: TransitionLevelSetView; zpc_amd/csrc/levelset_transition.hip):
+ * the blend of two level sets a keyframe spacing stepDt apart at the phase alpha between them, the reference's TransitionLevelSetView
+ * over the two front entries of its keyframe queue (geometry/LevelSet.h).  With v = (src.v(x) + dst.v(x)) / 2, x0 = x - alpha stepDt v and
+ * x1 = x + (1 - alpha) stepDt v every level-set call is (1 - alpha) src.call(x0) + alpha dst.call(x1); a level set without "v" counts as
+ * v = 0.  The float32 operation order is fixed in levelset_device.hpp.  src and dst may be the same level set (a queue of one keyframe).
+ * maxSpeed: an upper bound of |v_d| over both level sets' "v" cells and backgrounds (zs_rocm_levelset_max_speed).  It only sizes the
+ * block kernels' staged footprints: a cell outside a staged box is read from the grid, so every evaluated node gets the same bits
+ * whatever the bound, and a bound that is too large only costs time.  The cull takes the footprint to hold every read: a bound that is
+ * too SMALL by more than the footprint's pad (displacements over ~1.75 cells beyond it) may cull a block that holds an inside node.
+ * The block kernels add their per-block path counts to src.stats (NULL: not counted), FOUR device words -- all four are written, unlike
+ * the single level set's three: [0] culled, [1] evaluated with both sdf boxes staged, [2] evaluated with at least one level set read
+ * through direct hash queries, [3] those of [1] where a "v" box did not fit the LDS budget and was read directly.
+ * The cull trusts maxSpeed: a block is culled when neither staged sdf box holds a negative value, and the boxes cover the displaced
+ * samples only if maxSpeed really bounds |v_d|.  A bound that is too LARGE costs time only.  One that is too SMALL leaves every evaluated
+ * node's bits as they are, but once the real displacement exceeds the box's pad (1.75 cells + the widening) a block holding an inside
+ * node can be culled: fill maxSpeed from zs_rocm_levelset_max_speed and the backgrounds, never from a guess. */
+typedef struct zs_rocm_levelset_transition {
+  zs_rocm_levelset src, dst;
+  float stepDt, alpha, maxSpeed;
+} zs_rocm_levelset_transition;
+/* The calls below validate first and return -1 with nothing written: both level sets as above, alpha in [0, 1], stepDt and maxSpeed
+ * finite and >= 0. */
+/* *out (one device word) = the largest |v_d| over the three "v" channels of all cells of all stored blocks, 0 without "v" (the
+ * reference's get_level_set_max_speed samples at the cell centres, which returns the cell values) */
+ZS_ROCM_EXPORT int zs_rocm_levelset_max_speed(zs_rocm_policy *, const zs_rocm_levelset *, float *out);
+/* zs_rocm_levelset_sample / zs_rocm_levelset_collider_resolve on the transition */
+ZS_ROCM_EXPORT int zs_rocm_levelset_transition_sample(zs_rocm_policy *, const zs_rocm_levelset_transition *, const float *x, size_t n, float *sdf,
+                                                      float *normal, float *vel);
+ZS_ROCM_EXPORT int zs_rocm_levelset_transition_collider_resolve(zs_rocm_policy *, const zs_rocm_collider *collider,
+                                                                const zs_rocm_levelset_transition *, const float *x, float *v, size_t n,
+                                                                int *inside);
+/* the three grid-pass entries above with the transition as the shape: one workgroup per grid block stages both level sets' footprints,
+ * widened by the largest displacement of a sample point; every node gets the bits zs_rocm_levelset_transition_collider_resolve gives */
+ZS_ROCM_EXPORT int zs_rocm_mpm_apply_boundary_transition(zs_rocm_policy *, const zs_rocm_mpm_params *, const zs_rocm_bht_3 *, float *grid,
+                                                         size_t nblocks, const zs_rocm_collider *collider, const zs_rocm_levelset_transition *);
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_project_transition(zs_rocm_policy *, const zs_rocm_mpm_params *, const zs_rocm_bht_3 *, const float *grid,
+                                                           size_t nblocks, const zs_rocm_collider *collider,
+                                                           const zs_rocm_levelset_transition *, float *inout);
+ZS_ROCM_EXPORT int zs_rocm_mpm_implicit_solve_transition(zs_rocm_policy *, const zs_rocm_mpm_params *, zs_rocm_particles, const zs_rocm_bht_3 *,
+                                                         const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount,
+                                                         const int *nbr, const zs_rocm_collider *collider,
+                                                         const zs_rocm_levelset_transition *, const float *b, float *x, int maxIters, float tol,
+                                                         float relTol, int *iters);
 /* ---- triangle meshes as colliders (include/zensim_rocm/mesh_device.hpp, zpc_amd/csrc/mesh.hip): the bulk form of
  * `pol(range(n), [bvh = proxy<space>(bvh)](i){ bvh.find_nearest(p, f, cap); })` (LBvhView::find_nearest, container/Bvh.hpp:547-590) with the
  * point-triangle distance of geometry/SpatialQuery.hpp:19-315 (dist_pt_sqr / pt_category_and_dist2) as the functor f, and the conversion

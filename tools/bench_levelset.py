@@ -42,7 +42,7 @@ def timed(pol, fn, reps, warmup):
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
     a = np.asarray(ms)
-    return dict(median_ms=float(np.median(a)), p10_ms=float(np.percentile(a, 10)), p90_ms=float(np.percentile(a, 90)), min_ms=float(a.min()),
+    return dict(mean_ms=float(a.mean()), median_ms=float(np.median(a)), p10_ms=float(np.percentile(a, 10)), p90_ms=float(np.percentile(a, 90)), min_ms=float(a.min()),
                 max_ms=float(a.max()), reps=reps)
 
 

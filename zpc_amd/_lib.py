@@ -115,6 +115,11 @@ class LevelSet(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+class LevelSetTransition(C.Structure):
+    """zs_rocm_levelset_transition (include/zs_rocm.h): two level sets, the keyframe spacing, the phase between them and the speed bound"""
+    _fields_ = [("src", LevelSet), ("dst", LevelSet), ("stepDt", C.c_float), ("alpha", C.c_float), ("maxSpeed", C.c_float)]
+
+
 class MeshView(C.Structure):
     """zs_rocm_mesh_view (include/zs_rocm.h): the arrays of a triangle mesh object, all device pointers"""
     _fields_ = [("verts", C.c_void_p), ("tris", C.c_void_p), ("vel", C.c_void_p), ("faceNormals", C.c_void_p), ("vertNormals", C.c_void_p),
@@ -428,6 +433,17 @@ def _declare_containers(L):
                                                       C.POINTER(C.c_int)]
     for name in ("levelset_sample", "levelset_collider_resolve", "mpm_apply_boundary_levelset", "mpm_implicit_project_levelset",
                  "mpm_implicit_solve_levelset"):
+        getattr(L, "zs_rocm_" + name).restype = i32
+    PT = C.POINTER(LevelSetTransition)
+    L.zs_rocm_levelset_max_speed.argtypes = [vp, PL, vp]
+    L.zs_rocm_levelset_transition_sample.argtypes = [vp, PT, vp, sz, vp, vp, vp]
+    L.zs_rocm_levelset_transition_collider_resolve.argtypes = [vp, PC, PT, vp, vp, sz, vp]
+    L.zs_rocm_mpm_apply_boundary_transition.argtypes = [vp, PP, vp, vp, sz, PC, PT]
+    L.zs_rocm_mpm_implicit_project_transition.argtypes = [vp, PP, vp, vp, sz, PC, PT, vp]
+    L.zs_rocm_mpm_implicit_solve_transition.argtypes = [vp, PP, Particles, vp, vp, sz, vp, vp, vp, PC, PT, vp, vp, i32, f32, f32,
+                                                        C.POINTER(C.c_int)]
+    for name in ("levelset_max_speed", "levelset_transition_sample", "levelset_transition_collider_resolve", "mpm_apply_boundary_transition",
+                 "mpm_implicit_project_transition", "mpm_implicit_solve_transition"):
         getattr(L, "zs_rocm_" + name).restype = i32
     L.zs_rocm_mesh_create.argtypes = [vp, vp, sz, vp, sz, vp]
     L.zs_rocm_mesh_create.restype = vp

@@ -28,6 +28,8 @@ EXTRA_FLAGS = {"mpm_slotted.hip": ["-fno-slp-vectorize"], "mpm_slotblk.hip": ["-
                "collider.hip": ["-ffp-contract=off"], "mpm_implicit_project.hip": ["-ffp-contract=off"],
                # the level-set normal is a float central difference at +- h / 4 (include/zensim_rocm/levelset_device.hpp)
                "levelset.hip": ["-ffp-contract=off"],
+               # the transition between two level sets: the tests reproduce its float32 chain up to the displaced sample points
+               "levelset_transition.hip": ["-ffp-contract=off"],
                # point-triangle distances and pseudonormal signs (include/zensim_rocm/distance_device.hpp): a float32 chain in numpy
                # reproduces the discrete decisions (region, nearest triangle, sign) only without fused multiply-adds
                "mesh.hip": ["-ffp-contract=off"]}
@@ -75,7 +77,10 @@ def build_hip(force=False, verbose=True):
 #                   FP contraction like every translation unit that evaluates a level set
 #   test_mesh       TriMeshView::signed_distance / closest_point in a user lambda against the C ABI's bulk entries; built without FP
 #                   contraction like every translation unit that uses the point-triangle distance
-CPP_TESTS = {"test_cpp_face": ["-munsafe-fp-atomics"], "test_ofb": [], "test_levelset": ["-ffp-contract=off"], "test_mesh": ["-ffp-contract=off"]}
+#   test_transition TransitionLevelSetView{viewA, viewB, stepDt, alpha} and Collider over it in a user lambda against the C ABI's transition
+#                   entries; without FP contraction for the same reason
+CPP_TESTS = {"test_cpp_face": ["-munsafe-fp-atomics"], "test_ofb": [], "test_levelset": ["-ffp-contract=off"], "test_mesh": ["-ffp-contract=off"],
+             "test_transition": ["-ffp-contract=off"]}
 
 
 def build_cpp_test(name, verbose=True):

@@ -151,6 +151,11 @@ int mpm_g2p2g_slots_signal(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_
 bool levelset_collider_ok(const zs_rocm_collider *collider, const zs_rocm_levelset *levelset);
 void levelset_blocks_enqueue(hipStream_t stream, const zs_rocm_mpm_params *p, const int *activeKeys, float *grid, size_t nblocks,
                              const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, float *dof);
+bool levelset_ok(const zs_rocm_levelset *levelset);
+// levelset_transition.hip: the same for a (collider, transition) pair; false when the launch failed
+bool transition_collider_ok(const zs_rocm_collider *collider, const zs_rocm_levelset_transition *transition);
+bool transition_blocks_enqueue(hipStream_t stream, const zs_rocm_mpm_params *p, const int *activeKeys, float *grid, size_t nblocks,
+                               const zs_rocm_collider *collider, const zs_rocm_levelset_transition *transition, float *dof);
 
 }  // namespace zsr
 

@@ -186,15 +186,26 @@ static void implicit_precondition(Launch &L, const float *grid, size_t nblocks, 
   if (side == 4) hipLaunchKernelGGL((implicit_precondition_kernel<4>), dim3(ceil_div(ne, 256)), dim3(256), 0, L.stream, grid, in, out, ne);
   else hipLaunchKernelGGL((implicit_precondition_kernel<8>), dim3(ceil_div(ne, 256)), dim3(256), 0, L.stream, grid, in, out, ne);
 }
-// levelset set: `collider` gives type and motion, the level set the shape (the grid is only read there too)
-static void implicit_project(Launch &L, const ImplicitArgs &a, const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, float *inout) {
+// the shape of the projection's collider: none (the collider's own analytic shape), a level set, or a transition between two
+struct BoundaryShape {
+  const zs_rocm_levelset *levelset = nullptr;
+  const zs_rocm_levelset_transition *transition = nullptr;
+  explicit operator bool() const { return levelset || transition; }
+};
+// shape set: `collider` gives type and motion only (the grid is only read there too)
+// false: the transition kernel could not be launched
+static bool implicit_project(Launch &L, const ImplicitArgs &a, const zs_rocm_collider *collider, const BoundaryShape &shape, float *inout) {
   const int *keys = (const int *)a.tab->t.dev().activeKeys;
+  const zs_rocm_levelset *levelset = shape.levelset;
+  if (shape.transition) return transition_blocks_enqueue(L.stream, a.p, keys, const_cast<float *>(a.grid), a.nblocks, collider, shape.transition, inout);
   if (levelset) levelset_blocks_enqueue(L.stream, a.p, keys, const_cast<float *>(a.grid), a.nblocks, collider, levelset, inout);
   else implicit_project_enqueue(L.stream, a.p, keys, a.grid, a.nblocks, collider, inout);
+  return true;
 }
-// a level set comes with a collider (type and motion); neither: no boundary
-static bool boundary_ok(const zs_rocm_collider *collider, const zs_rocm_levelset *levelset) {
-  return levelset ? levelset_collider_ok(collider, levelset) : true;
+// a level set or a transition comes with a collider (type and motion); neither: no boundary
+static bool boundary_ok(const zs_rocm_collider *collider, const BoundaryShape &shape) {
+  if (shape.transition) return transition_collider_ok(collider, shape.transition);
+  return shape.levelset ? levelset_collider_ok(collider, shape.levelset) : true;
 }
 
 }  // namespace zsr
@@ -225,22 +236,27 @@ int zs_rocm_mpm_implicit_multiply(zs_rocm_policy *pol, const zs_rocm_mpm_params 
 }
 
 static int implicit_project_entry(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, const zs_rocm_bht_3 *tab, const float *grid, size_t nblocks,
-                                  const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, float *inout) {
+                                  const zs_rocm_collider *collider, const BoundaryShape &levelset, float *inout) {
   if (!pol || !p || !tab || !grid || !inout || (p->side != 4 && p->side != 8) || !(p->dx > 0.f)) return -1;
   if (!boundary_ok(collider, levelset) || nblocks > (size_t)0x7fffffff) return -1;
   Launch L(pol, "ImplicitMPMSystem::project");
   const ImplicitArgs a{p, zs_rocm_particles{}, tab, grid, nblocks, nullptr, nullptr, nullptr};
-  implicit_project(L, a, collider, levelset, inout);
-  return 0;
+  return implicit_project(L, a, collider, levelset, inout) ? 0 : -1;
 }
 int zs_rocm_mpm_implicit_project(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, const zs_rocm_bht_3 *tab, const float *grid, size_t nblocks,
                                  const zs_rocm_collider *collider, float *inout) {
-  return implicit_project_entry(pol, p, tab, grid, nblocks, collider, nullptr, inout);
+  return implicit_project_entry(pol, p, tab, grid, nblocks, collider, BoundaryShape{}, inout);
 }
 int zs_rocm_mpm_implicit_project_levelset(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, const zs_rocm_bht_3 *tab, const float *grid,
                                           size_t nblocks, const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, float *inout) {
   if (!levelset && collider) return -1;  // (a collider alone is zs_rocm_mpm_implicit_project's)
-  return implicit_project_entry(pol, p, tab, grid, nblocks, collider, levelset, inout);
+  return implicit_project_entry(pol, p, tab, grid, nblocks, collider, BoundaryShape{levelset, nullptr}, inout);
+}
+int zs_rocm_mpm_implicit_project_transition(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, const zs_rocm_bht_3 *tab, const float *grid,
+                                            size_t nblocks, const zs_rocm_collider *collider, const zs_rocm_levelset_transition *transition,
+                                            float *inout) {
+  if (!transition) return -1;
+  return implicit_project_entry(pol, p, tab, grid, nblocks, collider, BoundaryShape{nullptr, transition}, inout);
 }
 
 int zs_rocm_mpm_implicit_precondition(zs_rocm_policy *pol, const float *grid, size_t nblocks, int side, const float *in, float *out) {
@@ -282,7 +298,7 @@ void zs_rocm_dof_dot(zs_rocm_policy *pol, const float *a, const float *b, size_t
 // the CG driver of both solve entries
 static int implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab, const float *grid,
                           size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr, const zs_rocm_collider *collider,
-                          const zs_rocm_levelset *levelset, const float *b, float *x, int maxIters, float tol, float relTol, int *iters) {
+                          const BoundaryShape &levelset, const float *b, float *x, int maxIters, float tol, float relTol, int *iters) {
   const ImplicitArgs a{p, ps, tab, grid, nblocks, binStart, cellCount, nbr};
   if (!pol || !implicit_args_ok(a, true) || !b || !x || b == x || maxIters < 0) return -1;
   if (!boundary_ok(collider, levelset) || nblocks > (size_t)0x7fffffff) return -1;
@@ -298,7 +314,7 @@ static int implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_r
   // (the reference copies xinout into a member x_ first and back at the end, :77,160: x is updated in place here)
   implicit_multiply(L, a, x, temp, stale);
   dof_compwise(L, DOF_MINUS, b, temp, r, ne);  // r = b - A x
-  implicit_project(L, a, collider, levelset, r);
+  if (!implicit_project(L, a, collider, levelset, r)) return -1;
   dof_assign(L, r, q, ne);                     // (entries without mass: q keeps r there, which the projection has zeroed)
   implicit_precondition(L, grid, nblocks, p->side, r, q);
   dof_assign(L, q, pv, ne);
@@ -310,7 +326,7 @@ static int implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_r
   for (; iter != maxIters; ++iter) {
     if (resNorm <= localTol) break;
     implicit_multiply(L, a, pv, temp, stale);
-    implicit_project(L, a, collider, levelset, temp);
+    if (!implicit_project(L, a, collider, levelset, temp)) return -1;
     dof_dot(L, temp, pv, ne, partials, scalar);
     const float alpha = zTrk / read_back(L, scalar);
     dof_linear_combine(L, alpha, pv, 1.f, x, x, ne);      // x = x + alpha p
@@ -329,14 +345,23 @@ static int implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_r
 int zs_rocm_mpm_implicit_solve(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab,
                                const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr,
                                const zs_rocm_collider *collider, const float *b, float *x, int maxIters, float tol, float relTol, int *iters) {
-  return implicit_solve(pol, p, ps, tab, grid, nblocks, binStart, cellCount, nbr, collider, nullptr, b, x, maxIters, tol, relTol, iters);
+  return implicit_solve(pol, p, ps, tab, grid, nblocks, binStart, cellCount, nbr, collider, BoundaryShape{}, b, x, maxIters, tol, relTol, iters);
 }
 int zs_rocm_mpm_implicit_solve_levelset(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab,
                                         const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr,
                                         const zs_rocm_collider *collider, const zs_rocm_levelset *levelset, const float *b, float *x,
                                         int maxIters, float tol, float relTol, int *iters) {
   if (!levelset && collider) return -1;  // (a collider alone is zs_rocm_mpm_implicit_solve's)
-  return implicit_solve(pol, p, ps, tab, grid, nblocks, binStart, cellCount, nbr, collider, levelset, b, x, maxIters, tol, relTol, iters);
+  return implicit_solve(pol, p, ps, tab, grid, nblocks, binStart, cellCount, nbr, collider, BoundaryShape{levelset, nullptr}, b, x, maxIters, tol,
+                        relTol, iters);
+}
+int zs_rocm_mpm_implicit_solve_transition(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab,
+                                          const float *grid, size_t nblocks, const int *binStart, const unsigned *cellCount, const int *nbr,
+                                          const zs_rocm_collider *collider, const zs_rocm_levelset_transition *transition, const float *b,
+                                          float *x, int maxIters, float tol, float relTol, int *iters) {
+  if (!transition) return -1;
+  return implicit_solve(pol, p, ps, tab, grid, nblocks, binStart, cellCount, nbr, collider, BoundaryShape{nullptr, transition}, b, x, maxIters,
+                        tol, relTol, iters);
 }
 
 }  // extern "C"

@@ -1,12 +1,13 @@
 """Sparse level sets: zs::LevelSetBoundary<SparseGrid<3, f32, 8>> (geometry/Collider.h:246-252, geometry/SparseGrid.hpp) built from a
 dense signed-distance array -- a bht<int, 3, int, 16> keyed by block origins next to a TileVector<f32, 512> with the properties "sdf"
 (1 channel) and optionally "v" (3 channels) -- for MpmTransfer.apply_boundary / implicit_project / implicit_solve / step_slotted
-(levelset=).  Set-up code: numpy and torch for the plumbing, the library's containers for the storage."""
+(levelset=), and LevelSetSequence, the queue of keyframes whose two front entries those calls blend (an animated collider rebuilt once
+per frame instead of once per sub-step).  Set-up code: numpy and torch for the plumbing, the library's containers for the storage."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, LevelSet
+from ._lib import lib, LevelSet, LevelSetTransition
 from .containers import Bht, TileVector
 
 SIDE, BLOCK = 8, 512   # SparseGrid<3, f32, 8>
@@ -183,6 +184,16 @@ class SparseLevelSet:
             C.CDLL("libamdhip64.so").hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(self.table.view().activeKeys), C.c_size_t(a.nbytes), 2)
         return a
 
+    def max_speed(self):
+        """the largest |v_d| over the three "v" channels of all cells of all stored blocks (get_level_set_max_speed,
+        geometry/LevelSetUtils.tpp), 0.0 without "v"; reduced on the device, synchronises the stream"""
+        import torch
+        out = torch.empty(1, dtype=torch.float32, device="cuda")
+        if lib().zs_rocm_levelset_max_speed(self.pol.handle, C.byref(self.view), out.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_levelset_max_speed refused its arguments")
+        self.pol.syncCtx()
+        return float(out.item())
+
     def enable_stats(self):
         """count, per block-kernel launch and grid block, how the block was handled: stats()[0] culled, [1] staged, [2] direct"""
         import torch
@@ -223,3 +234,89 @@ class SparseLevelSet:
                 out[a[0] - lo[0]:e[0] - lo[0], a[1] - lo[1]:e[1] - lo[1], a[2] - lo[2]:e[2] - lo[2]] = \
                     tiles[b, a[0] - o[0]:e[0] - o[0], a[1] - o[1]:e[1] - o[1], a[2] - o[2]:e[2] - o[2]]
         return out
+
+
+POP_THRESHOLD = np.float32(1) - np.float32(128) * np.finfo(np.float32).eps
+
+
+class LevelSetSequence:
+    """The keyframe queue of the reference's ConstTransitionLevelSetPtr (geometry/LevelSet.h): push(level set) appends a keyframe, the two
+    front ones are blended at the phase alpha (TransitionLevelSetView, include/zensim_rocm/levelset_device.hpp), advance(ratio) moves
+    the phase and drops the front keyframe each time it passes 1.  step_dt: the time between two keyframes.  Pass the sequence (or its
+    view()) as levelset= to MpmTransfer.apply_boundary / implicit_project / implicit_solve / step_slotted.  alpha is kept in float32."""
+
+    def __init__(self, pol, step_dt):
+        self.pol = pol
+        self.fields = []        # [(level set, its speed bound)]
+        self.alpha = np.float32(0)
+        self.stats = None
+        self.set_step_dt(step_dt)
+
+    def set_step_dt(self, step_dt):
+        if not (np.isfinite(step_dt) and step_dt >= 0):
+            raise ValueError("step_dt: finite and not negative")
+        self.step_dt = float(np.float32(step_dt))
+
+    def __len__(self):
+        return len(self.fields)
+
+    @staticmethod
+    def speed_bound(ls):
+        """max |v_d| a sample of ls can return: its cells and its background; 0 without a "v" property"""
+        return max(ls.max_speed(), abs(float(np.float32(ls.background)))) if ls.has_velocity else 0.0
+
+    def push(self, ls, allow_wide=False):
+        """append a keyframe.  A sample point moves by up to step_dt * speed before a level set is asked: beyond that level set's band
+        its stencil may be constant, the blended distance can then be negative where neither keyframe is, and the normal is 0 / 0 (as in
+        the reference), so this raises ValueError when step_dt * speed exceeds the band; allow_wide=True takes the keyframe anyway.  A
+        level set that does not know its band (built from keys and cells directly) is not checked."""
+        speed = self.speed_bound(ls)
+        band = getattr(ls, "band", None)
+        if not allow_wide and band is not None and self.step_dt * speed > band:
+            raise ValueError("push: step_dt * max speed = %g exceeds the level set's band %g (allow_wide=True overrides)"
+                             % (self.step_dt * speed, band))
+        self.fields.append((ls, speed))
+
+    def push_from_mesh(self, mesh, voxel, band, allow_wide=False, **kw):
+        """push(SparseLevelSet.from_mesh(pol, mesh, voxel, band, **kw)); returns the level set"""
+        ls = SparseLevelSet.from_mesh(self.pol, mesh, voxel, band, **kw)
+        self.push(ls, allow_wide=allow_wide)
+        return ls
+
+    def pop(self):
+        self.fields.pop(0)
+
+    def advance(self, ratio):
+        """alpha += ratio; while alpha > 1 - 128 eps: alpha -= 1 and the front keyframe (if any) is dropped -- in float32"""
+        self.alpha = np.float32(self.alpha + np.float32(ratio))
+        while self.alpha > POP_THRESHOLD:
+            self.alpha = np.float32(self.alpha - np.float32(1))
+            if self.fields:
+                self.pop()
+
+    def enable_stats(self):
+        """count how the block kernels handled each grid block: read_stats()[0] culled, [1] staged, [2] direct, [3] staged with a "v" box
+        read directly"""
+        import torch
+        self.stats = torch.zeros(4, dtype=torch.int32, device="cuda")
+
+    def read_stats(self, reset=True):
+        self.pol.syncCtx()
+        s = self.stats.cpu().numpy().astype(np.int64)
+        if reset:
+            self.stats.zero_()
+        return s
+
+    def view(self):
+        """the zs_rocm_levelset_transition of the two front keyframes (dst = src with one); the sequence keeps them alive until the next
+        view().  Raises on an empty queue."""
+        if not self.fields:
+            raise RuntimeError("the level-set transition queue is empty")
+        (src, s0), (dst, s1) = self.fields[0], self.fields[1 if len(self.fields) > 1 else 0]
+        t = LevelSetTransition()
+        t.src = type(src.view).from_buffer_copy(bytes(src.view))
+        t.dst = type(dst.view).from_buffer_copy(bytes(dst.view))
+        t.src.stats = self.stats.data_ptr() if self.stats is not None else None
+        t.stepDt, t.alpha, t.maxSpeed = self.step_dt, float(self.alpha), max(s0, s1)
+        self._alive = (src, dst, t)
+        return t

@@ -466,6 +466,12 @@ class MpmTransfer:
         """ApplyBoundaryConditionOnGridBlocks (simulation/grid/GridOp.hpp:111-164): collider.resolveCollision on every grid node
         with mass; call after grid_update.  `collider`: make_collider(...); with levelset= (a SparseLevelSet or its .view):
         make_levelset_collider(...), the level set is the shape."""
+        tr = _transition_view(levelset)
+        if tr is not None:
+            if lib().zs_rocm_mpm_apply_boundary_transition(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(),
+                                                           self.nblocks, C.byref(collider), C.byref(tr)) != 0:
+                raise RuntimeError("zs_rocm_mpm_apply_boundary_transition refused its arguments")
+            return
         if levelset is not None:
             if lib().zs_rocm_mpm_apply_boundary_levelset(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(),
                                                          self.nblocks, C.byref(collider), C.byref(_levelset_view(levelset))) != 0:
@@ -523,6 +529,13 @@ class MpmTransfer:
         """ImplicitMPMSystem::project: resolveCollision on nodes with mass, nodes without mass zeroed; collider None: only the zeroing.
         levelset=: the collider (make_levelset_collider) takes its shape from that level set."""
         self._check_dof(inout)
+        tr = _transition_view(levelset)
+        if tr is not None:
+            if lib().zs_rocm_mpm_implicit_project_transition(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(),
+                                                             self.nblocks, C.byref(collider) if collider is not None else None,
+                                                             C.byref(tr), inout.data_ptr()) != 0:
+                raise RuntimeError("zs_rocm_mpm_implicit_project_transition refused its arguments")
+            return
         if levelset is not None:
             if lib().zs_rocm_mpm_implicit_project_levelset(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(),
                                                            self.nblocks, C.byref(collider) if collider is not None else None,
@@ -546,6 +559,14 @@ class MpmTransfer:
         self._check_dof(b, x)
         bs, cc, nb = self._bins(binned)
         it = C.c_int(0)
+        tr = _transition_view(levelset)
+        if tr is not None:
+            if lib().zs_rocm_mpm_implicit_solve_transition(self.pol.handle, C.byref(self.params), self.particles(), self.table.handle,
+                                                           self.grid.data_ptr(), self.nblocks, bs, cc, nb,
+                                                           C.byref(collider) if collider is not None else None, C.byref(tr),
+                                                           b.data_ptr(), x.data_ptr(), int(max_iters), float(tol), float(rel_tol), C.byref(it)) != 0:
+                raise RuntimeError("zs_rocm_mpm_implicit_solve_transition refused its arguments")
+            return it.value
         if levelset is not None:
             if lib().zs_rocm_mpm_implicit_solve_levelset(self.pol.handle, C.byref(self.params), self.particles(), self.table.handle,
                                                          self.grid.data_ptr(), self.nblocks, bs, cc, nb,
@@ -672,8 +693,19 @@ class MpmTransfer:
         boundary blocks [0, n_boundary) then the interior, ghost-block exchange of `plan` on comm_pol's stream overlapping the interior,
         grid update (+ collider), CFL allreduce(max) of max_vel.  The grids swap: self.grid is the new one afterwards.
         comm: NativeComm, plan: NativeHaloPlan (both None on a single rank).  levelset=: the boundary is that level set with `collider`'s
-        (make_levelset_collider) type and motion."""
+        (make_levelset_collider) type and motion.  A LevelSetSequence (or its view()) as levelset= is served by two calls on the policy's
+        stream: this step without a collider, then zs_rocm_mpm_apply_boundary_transition on the new grid (single rank only).  max_vel is
+        then the maximum BEFORE the boundary pass (the one-call paths take it after their collider): take the collider's own speed into
+        account in a CFL estimate made from it."""
         assert self.slotted
+        tr = _transition_view(levelset)
+        if tr is not None:
+            if collider is None or comm is not None or plan is not None:
+                raise RuntimeError("step_slotted: a level-set sequence needs a collider (type and motion) and runs on a single rank")
+            self.step_slotted(extf, max_vel, write_all, n_boundary, None, None, comm_pol, None, halo_grid, events, breakdown, halo_channels,
+                              range_schedule, handover_snapshot, None)
+            self.apply_boundary(collider, levelset=tr)
+            return
         if getattr(self, "grid2", None) is None or self.grid2.numel() != self.grid.numel():
             self.grid2 = torch.empty_like(self.grid)
         src, dst = self.grid, self.grid2
@@ -875,6 +907,15 @@ def make_levelset_collider(ctype, s=1.0, dsdt=0.0, R=None, omega=(0, 0, 0), b=(0
     collider a level set (zpc_amd.levelset.SparseLevelSet, passed as levelset=) gives the shape to.  The defaults are the identity
     transform the reference's two call sites build (GridOp.hpp:128-134, ImplicitMPM.hpp:110-114)."""
     return make_collider(PLANE, ctype, (), s=s, dsdt=dsdt, R=R, omega=omega, b=b, dbdt=dbdt)   # (geometry / param are not read)
+
+
+def _transition_view(levelset):
+    """the ctypes zs_rocm_levelset_transition of a LevelSetSequence (or the struct itself); None for anything else"""
+    from ._lib import LevelSetTransition
+    from .levelset import LevelSetSequence
+    if isinstance(levelset, LevelSetTransition):
+        return levelset
+    return levelset.view() if isinstance(levelset, LevelSetSequence) else None
 
 
 def _levelset_view(levelset):
