@@ -6,7 +6,9 @@ hide under the channel maximum.  The channel-max checks of the other modules sta
 Force channels: where the kernel read the cached P F^T vol, the test reads the same 6 components back (mt.off["PF"]) and the force is
 checked to rounding.  Where the step computed the stress itself (stress inside P2G, the fused steps), the force is checked against the
 oracle's stress of the stored state with the stress tolerance of test_svd_and_stress_blocks (1e-4 of the row scale) as e_in, and only
-for FixedCorotated, whose F is stored unprojected.  With write_all the stored stress is stress_pack of the 9-component PF the scatter
+for FixedCorotated, whose F is stored unprojected.  That tolerance is kernel against oracle, the same algorithm in the same precision; how
+far both are from the float64 stress (up to 1e-2 of the scale away from F = I), and the kernels' own stress sample by sample on every
+model and branch, is the subject of tests/ref64_stress.py and tests/test_stress_ref64_gpu.py.  With write_all the stored stress is stress_pack of the 9-component PF the scatter
 used; its symmetric part is compared with the oracle's under the same tolerance (the off-diagonal pairs differ by the SVD's rounding,
 not by a multiple of u).  Prints one `REF64 <path> <worst err/bound per channel>` line per check."""
 import ctypes as C

@@ -340,3 +340,73 @@ def code_object_kernels(obj, workdir, co_name="p.co"):
         if ".name" in meta:
             kernels.append((meta[".name"], meta, size[meta[".name"]]))
     return kernels, co
+
+
+# ---------------------------------------------------------------------------------------- per-sample oracle SVD / stress (ref64_stress)
+_ORC_STRESS_CACHE = {}
+
+
+def _proto(oracle, name, argtypes):
+    """a private prototype of an oracle function: the argument types of the shared CDLL's own attribute stay as other tests set them"""
+    return C.CFUNCTYPE(None, *argtypes)((name, oracle))
+
+
+def oracle_svd_all(oracle, F):
+    """orc_svd3 of every row of F [n, 9] float32 -> U [n, 9], S [n, 3], V [n, 9]"""
+    F = np.ascontiguousarray(F, np.float32)
+    n = len(F)
+    Uo, So, Vo = np.zeros((n, 9), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 9), np.float32)
+    f = _proto(oracle, "orc_svd3", [C.c_void_p] * 4)
+    pF, pU, pS, pV = F.ctypes.data, Uo.ctypes.data, So.ctypes.data, Vo.ctypes.data
+    for i in range(n):
+        f(pF + 36 * i, pU + 36 * i, pS + 12 * i, pV + 36 * i)
+    return Uo, So, Vo
+
+
+def oracle_stress_all(oracle, m, F, lj, key=None):
+    """the oracle's constitutive update of every sample: m is a ref64_stress.Material (models 0-3; CUDA-header variants of von Mises
+    and NACC).  Returns P F^T vol [n, 9], the projected F [n, 9] and the new logJp [n] (copies; cached under `key`, which names the
+    inputs, together with the material's values)."""
+    if key is not None:
+        key = (key, tuple(sorted(vars(m).items())))
+    if key is not None and key in _ORC_STRESS_CACHE:
+        return tuple(a.copy() for a in _ORC_STRESS_CACHE[key])
+    Fo = np.ascontiguousarray(F, np.float32).copy()
+    ljo = np.ascontiguousarray(lj, np.float32).copy()
+    n = len(Fo)
+    PF = np.zeros((n, 9), np.float32)
+    cf, vp = C.c_float, C.c_void_p
+    pF, pL, pP = Fo.ctypes.data, ljo.ctypes.data, PF.ctypes.data
+    if m.model == 0:
+        f = _proto(oracle, "orc_stress_fixedcorotated", [cf, cf, cf, vp, vp])
+        for i in range(n):
+            f(m.volume, m.mu, m.lam, pF + 36 * i, pP + 36 * i)
+    elif m.model == 1:
+        f = _proto(oracle, "orc_stress_sand", [cf, cf, cf, cf, cf, cf, C.c_int, vp, vp, vp])
+        for i in range(n):
+            f(m.volume, m.mu, m.lam, m.cohesion, m.beta, m.yield_surface, int(m.vol_correction), pL + 4 * i, pF + 36 * i, pP + 36 * i)
+    elif m.model == 2:
+        f = _proto(oracle, "orc_stress_vonmises", [cf, cf, cf, cf, C.c_int, vp, vp])
+        for i in range(n):
+            f(m.volume, m.mu, m.lam, m.yield_stress, 0, pF + 36 * i, pP + 36 * i)
+    else:
+        f = _proto(oracle, "orc_stress_nacc", [cf, cf, cf, cf, cf, cf, cf, C.c_int, C.c_int, vp, vp, vp])
+        for i in range(n):
+            f(m.volume, m.mu, m.lam, m.bm, m.xi, m.beta, m.Msqr, int(m.hardening), 0, pL + 4 * i, pF + 36 * i, pP + 36 * i)
+    if key is not None:
+        _ORC_STRESS_CACHE[key] = (PF.copy(), Fo.copy(), ljo.copy())
+    return PF, Fo, ljo
+
+
+def eos_f32(J, bulk, volume):
+    """stress_eos without viscosity in numpy float32, in the header's operation order -> P F^T vol [n, 9]"""
+    f = np.float32
+    J = np.asarray(J, f)
+    with np.errstate(all="ignore"):
+        J2 = J * J
+        J4 = J2 * J2
+        p = f(bulk) * (f(1) / (J * J2 * J4) - f(1))
+        d = (f(0) - p) * (f(volume) * J)
+    out = np.zeros((len(J), 9), f)
+    out[:, 0] = out[:, 4] = out[:, 8] = d
+    return out
