@@ -26,10 +26,19 @@
 //     loads and stores share vmcnt, so a spill reload inside the chunk loop waits for the record prefetch of the next chunk and for the
 //     particle stores just issued (profiles/r05_block_kernel.md, section 7; tests/test_host_cpu.py keeps it that way);
 //   * the bin's P2G arena has 8^3 nodes (ArenaBin8): a mover into a neighbour bin adds its 27 node terms there (plain LDS
-//     read-add-write) and they reach the grid with the bin's one flush -- no global atomics per mover.
+//     read-add-write) and they reach the grid with the bin's one flush -- no global atomics per mover;
+//   * the flush visits what can be non-zero, not the 512 nodes: the 6^3 core the register planes write (4 dense passes) and those 8 x 8
+//     faces of the shell a list entry of the bin has reached (a 6-bit mask kept while the lists are scattered; none at rest).  Every LDS
+//     read of a pass is issued before the first is used, and a pass writes zero over what it read: the arena is cleared once per
+//     workgroup, never per bin (blk_flush_nodes and the bin end of blk_consumer; profiles/block_flush.md).
 // The per-particle code (slot_produce_entry), the consumers' accumulation (g2p2g_consume_set), the mover protocol, slot_rehome_kernel
 // and slot_commit_kernel are those of mpm_slotted.hip; results differ only in summation order.
 #include "mpm_slot.hpp"
+// -DZS_SLOTBLK_CHECK_ARENA (a measurement build: tools/ab_build.sh check "-DZS_SLOTBLK_CHECK_ARENA" mpm_slotblk.hip, selected with
+// ZS_ROCM_LIB) asserts after every bin's flush that the flushing wave's channels of the arena are all zero.  Never in the product build.
+#ifdef ZS_SLOTBLK_CHECK_ARENA
+#include <cassert>
+#endif
 
 namespace zsr {
 
@@ -142,8 +151,10 @@ struct ArenaBin8 {
 // set CS of their 27 node terms into the bin's 8^3 arena `pa` (this wave's channels).  Two list entries per pass, lane = (entry parity,
 // stencil node); the two entries of a pass may share nodes, so the halves do their read-add-write one after the other (LDS operations of
 // a wave execute in order).  Weights and values: StencilNodeLane, as slot_xlist_scatter.
+// `faces` (per lane, ORed): the faces of the arena's shell the entries of this lane reach -- bit 2 d: node 0 of the stencil sits on arena
+// coordinate 0 of axis d (the entry's coordinate is 0), bit 2 d + 1: node 2 sits on coordinate 7 (the entry's coordinate is 5).
 template <int CS>
-__device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned *xq, int nx, int lane, float *pa) {
+__device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned *xq, int nx, int lane, float *pa, unsigned &faces) {
   using S = ConsumerSet<CS>;
   using A8 = ArenaBin8;
   const int node = lane & 31, half = lane >> 5;
@@ -162,7 +173,9 @@ __device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned
 #pragma unroll
       for (int q = 0; q < 3; ++q) Wt *= sn.weight(q, st[(1 + q) * 64]);
       // (the entry carries new cell + 1 per axis = the arena coordinate of the stencil's node 0)
-      an = A8::at((int)((e >> 10) & 7u) + sn.sel[0], (int)((e >> 13) & 7u) + sn.sel[1], (int)((e >> 16) & 7u) + sn.sel[2]);
+      const int ex = (int)((e >> 10) & 7u), ey = (int)((e >> 13) & 7u), ez = (int)((e >> 16) & 7u);
+      an = A8::at(ex + sn.sel[0], ey + sn.sel[1], ez + sn.sel[2]);
+      faces |= (ex == 0 ? 1u : 0u) | (ex == 5 ? 2u : 0u) | (ey == 0 ? 4u : 0u) | (ey == 5 ? 8u : 0u) | (ez == 0 ? 16u : 0u) | (ez == 5 ? 32u : 0u);
 #pragma unroll
       for (int q = 0; q < S::NA; ++q) val[q] = sn.value<CS>(st, Wt, q);
     }
@@ -173,6 +186,43 @@ __device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned
         for (int q = 0; q < S::NA; ++q) pa[q * A8::CH + an] += val[q];
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+  }
+}
+
+// The flush of a bin's arena (this wave's channels, `pa`) to grid B, NP passes of 64 nodes at once: node p of a lane sits at arena offset
+// aoff[p], node (gx, gy, gz)[p] in cells of this block (-1 .. 10 per axis).  Every LDS read of the NP passes -- the nodes' blocks and their
+// NA values -- is issued before the first is used (one round trip, none waits for another); the nodes are then written back as zero, so
+// the arena is clear again where it was read, and the non-zero values go to the grid, one float atomic each.  A node whose block is not in
+// the partition and that has mass is reported (status[2]).  CORE: no node lies below the block (gx, gy, gz >= 0).
+template <int CS, int NP, bool CORE>
+__device__ __forceinline__ void blk_flush_nodes(float *pa, const int (&aoff)[NP], const int (&gx)[NP], const int (&gy)[NP], const int (&gz)[NP],
+                                                const int *nbrBlk, const SlotArgs &A) {
+  using S = ConsumerSet<CS>;
+  constexpr int NC = 512;
+  int bn[NP];
+  float v[NP][S::NA];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    auto side = [](int g) { return !CORE && g < 0 ? 0 : (g >= 8 ? 2 : 1); };
+    bn[p] = nbrBlk[(side(gx[p]) * 3 + side(gy[p])) * 3 + side(gz[p])];
+#pragma unroll
+    for (int q = 0; q < S::NA; ++q) v[p][q] = pa[q * ArenaBin8::CH + aoff[p]];
+  }
+  asm volatile("" ::: "memory");  // (keeps the compiler from sinking the reads to their uses)
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int q = 0; q < S::NA; ++q) pa[q * ArenaBin8::CH + aoff[p]] = 0.f;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    if (bn[p] >= 0) {
+      float *gq = A.gridB + ((size_t)bn[p] * 7 + S::CH0) * NC + (((gx[p] & 7) * 8 + (gy[p] & 7)) * 8 + (gz[p] & 7));
+#pragma unroll
+      for (int q = 0; q < S::NA; ++q)
+        if (v[p][q] != 0.f) unsafeAtomicAdd(gq + q * NC, v[p][q]);
+    } else if (S::MASS && v[p][0] != 0.f) {
+      A.status[2] = 1;  // mass for a node whose block is not in the partition
     }
   }
 }
@@ -255,7 +305,6 @@ template <int CS>
 __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)[3], int blk, int lane, int G, const BlkShared &sh, const SlotArgs &A) {
   using S = ConsumerSet<CS>;
   using AL = ArenaBin8;
-  constexpr int NC = 512;
   const int cx = lane >> 4, cy = (lane >> 2) & 3, cz = lane & 3;
   const unsigned long long lt = lanemask_lt();
   const float *const stage = sh.stage;
@@ -266,7 +315,12 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
 #pragma unroll
     for (int q = 0; q < S::NA; ++q) acc[k][q] = 0.f;
   unsigned mask = 0u;
+  unsigned faces = 0u;  // faces of the arena's shell the lists of the current bin have reached (blk_xlist_lds)
   int r = 0, off = 0;  // next round to consume, entry number of its first particle
+  // The bin's arena (this wave's channels) is cleared HERE, once: every flush leaves it all zero again (see the bin end below), and the
+  // padding of the 68-float stride is never written.
+  for (int k = lane; k < S::NA * AL::CH; k += 64) pa[k] = 0.f;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __syncthreads();  // (the producers' first record requests are out)
   // Per-bin state, kept by the consumers (off the producers' critical path; every buffer named here is dead for its previous owner, see the
   // file comment).  In iteration g, i.e. between the barriers "chunk g staged" and "chunk g + 1 staged", while the producers work on
@@ -296,8 +350,6 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
       r = 0;
       off = 0;
       mask = sh.masks[b][lane];
-      for (int k = lane; k < S::NA * AL::CH; k += 64) pa[k] = 0.f;  // the bin's arena (this wave's channels): the chunk lists add into it first
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
     const int produced = 256 * (c + 1) < total ? 256 * (c + 1) : total;
     const unsigned qn = sh.arrCnt[par][lane];
@@ -336,7 +388,7 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
     {
       const int nx = sh.xCnt[par] < (unsigned)SL_XQ ? (int)sh.xCnt[par] : SL_XQ;
       if (CS == 0 && lane == 0) sh.xCnt[(g + 2) % 3] = 0u;
-      blk_xlist_lds<CS>(stage, sh.xq[par], nx, lane, pa);
+      blk_xlist_lds<CS>(stage, sh.xq[par], nx, lane, pa, faces);
     }
     // this wave has read what it needs of chunk g: the producers may stage chunk g + 1 over it
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -345,27 +397,55 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
     if (CS == 3 && d[1].last()) blk_finish_bin(sh, A, blk * 8, b, d[1].qp(), lane);
     if (d[1].last()) {
       // last chunk of the bin: the set's channels of the bin's arena belong to this wave alone -- add the 27 register planes on top of
-      // the lists' terms (phases ordered inside the wave), send the arena's nodes to the grid; no other wave is involved
-      acc_to_arena<AL, true>(pa + AL::at(cx + 1, cy + 1, cz + 1), acc);
+      // the lists' terms (phases ordered inside the wave), send the arena's nodes to the grid; no other wave is involved.
+      //   * The register planes write the 6^3 CORE of the arena only (coordinates 1..6): it is flushed densely, 216 nodes in 4 passes
+      //     (the 40 idle lanes of the last pass read and zero a padding word).  A bin sits at offset 0 or 4 of its block, so a core node
+      //     lies in this block or in its +1 neighbour per axis.
+      //   * The 296 nodes of the SHELL (a coordinate 0 or 7) are written by the lists alone: a term at coordinate 0 of an axis comes from
+      //     node 0 of an entry whose coordinate on that axis is 0, a term at coordinate 7 from node 2 of an entry at coordinate 5 -- and
+      //     every such entry has set that face's bit in `faces`.  So every shell node that can be non-zero lies on a flagged face; the
+      //     flagged faces are flushed as 8 x 8 slabs, one pass each, and a bin without such movers (all of them at rest) flushes none.
+      //     Edges and corners belong to several faces: the first visit leaves them zero, the later ones skip them.
+      //   * Every pass writes zero over what it has read (LDS operations of a wave execute in order), so after the flush the wave's
+      //     channels are all zero again -- core: every node visited; shell: zero unless flagged -- and the next bin's lists add into a
+      //     clear arena without a clear loop of their own.
+      acc_to_arena<AL, true>(pa + AL::at(cx + 1, cy + 1, cz + 1), acc);  // (and the planes are zero again for the next bin)
       const SubGeom sg = sub_geom(borg, b);
-      for (int n = lane; n < 512; n += 64) {
-        const int x = n >> 6, y = (n >> 3) & 7, z = n & 7;
-        const int g[3] = {sg.o[0] - 1 + x, sg.o[1] - 1 + y, sg.o[2] - 1 + z};  // node in cells of this block: -1 .. 10
-        const int code = ((g[0] < 0 ? 0 : (g[0] >= 8 ? 2 : 1)) * 3 + (g[1] < 0 ? 0 : (g[1] >= 8 ? 2 : 1))) * 3 + (g[2] < 0 ? 0 : (g[2] >= 8 ? 2 : 1));
-        const int bn = sh.nbrBlk[code];
-        const float *a = pa + AL::at(x, y, z);
-        if (bn >= 0) {
-          float *gq = A.gridB + ((size_t)bn * 7 + S::CH0) * NC + (((g[0] & 7) * 8 + (g[1] & 7)) * 8 + (g[2] & 7));
+      // (the lane number made opaque: the node offsets below depend on the lane alone, and hoisted out of the chunk loop they would be
+      // a dozen registers carried across the accumulation -- the kernel has none to spare; recomputed per bin they cost ~60 VALU)
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      {
+        int aoff[4], gx[4], gy[4], gz[4];
 #pragma unroll
-          for (int q = 0; q < S::NA; ++q) {
-            const float v = a[q * AL::CH];
-            if (v != 0.f) unsafeAtomicAdd(gq + q * NC, v);
-          }
-        } else if (S::MASS && a[0] != 0.f) {
-          A.status[2] = 1;  // mass for a node whose block is not in the partition
+        for (int p = 0; p < 4; ++p) {
+          const int n = ln + 64 * p;
+          const int x = n / 36, y = (n / 6) % 6, z = n % 6;  // core node, 0..5 per axis
+          const bool in = p < 3 || n < 216;
+          aoff[p] = in ? AL::at(x + 1, y + 1, z + 1) : AL::at(0, 8, 0);  // (x = 0, word 64: padding, always zero)
+          gx[p] = in ? sg.o[0] + x : 0;
+          gy[p] = in ? sg.o[1] + y : 0;
+          gz[p] = in ? sg.o[2] + z : 0;
         }
+        blk_flush_nodes<CS, 4, true>(pa, aoff, gx, gy, gz, sh.nbrBlk, A);
       }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the arena is cleared again for the next bin only after these reads)
+      unsigned fm = 0u;  // (wave-uniform)
+#pragma unroll
+      for (int f = 0; f < 6; ++f) fm |= __ballot((faces >> f) & 1u) != 0ull ? 1u << f : 0u;
+      faces = 0u;
+#pragma unroll 1
+      while (fm) {
+        const int f = __builtin_ctz(fm);
+        fm &= fm - 1u;
+        const int ax = f >> 1, fix = (f & 1) * 7, u = ln >> 3, v = ln & 7;  // lane = the face's two free coordinates
+        const int x = ax == 0 ? fix : u, y = ax == 1 ? fix : (ax == 0 ? u : v), z = ax == 2 ? fix : v;
+        const int aoff[1] = {AL::at(x, y, z)}, gx[1] = {sg.o[0] - 1 + x}, gy[1] = {sg.o[1] - 1 + y}, gz[1] = {sg.o[2] - 1 + z};
+        blk_flush_nodes<CS, 1, false>(pa, aoff, gx, gy, gz, sh.nbrBlk, A);
+      }
+#ifdef ZS_SLOTBLK_CHECK_ARENA  // debug builds only (see the top of the file): the flush has left this wave's channels of the arena all zero
+      for (int k = lane; k < S::NA * AL::CH; k += 64) assert(pa[k] == 0.f);
+#endif
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next bin's lists add into the arena only after these writes)
     }
   }
   __syncthreads();  // the last bin is flushed
