@@ -1,4 +1,4 @@
-// distance_device.hpp -- squared distance from a point to a triangle with the closest point, its barycentric coordinates and the feature it
+// distance_device.hpp -- tri_closest: squared distance from a point to a triangle with the closest point, its barycentric coordinates and the feature it
 // lies on: the counterpart of dist_pt_sqr / pt_category_and_dist2 (geometry/SpatialQuery.hpp:19,146) and of pt_distance_type /
 // dist2_pt_unclassified (geometry/Distance.hpp), written from the Voronoi regions of a triangle (Ericson, Real-Time Collision Detection,
 // 5.1.5; Eberly, "Distance between point and triangle in 3D"):
@@ -10,6 +10,20 @@
 // noise below ~6e-8) skips the face test, so it degrades to the distance to its edges -- their union is its longest edge -- and, with all
 // three vertices equal, to the distance to that point (a zero-length edge has t = 0).  No division has a zero denominator: never a NaN
 // for finite input.
+//
+// ee_closest: squared distance between two segments [a0, a1] and [b0, b1] with the parameters of the closest point pair and the feature
+// pair it is realised on: the counterpart of dist_ee_sqr / ee_category_and_dist2 (geometry/SpatialQuery.hpp:316-500), same category
+// encoding (uCate * 3 + vCate, each 0: first endpoint, 1: second endpoint, 2: interior).  Written from the geometry, not from the
+// reference's clamped (a c - b^2) chain, whose absolute eps depends on the scale of the input and whose b e - c d cancels in float32:
+//   interior   with u = a1 - a0, v = b1 - b0, w = a0 - b0, n = u x v: the common perpendicular meets the lines at
+//              s = ((v x w) . n) / |n|^2, t = ((u x w) . n) / |n|^2.  A candidate only if the edges are not parallel
+//              (|n|^2 > EE_PARALLEL |u|^2 |v|^2, the threshold of TRI_DEGENERATE) and 0 < s < 1, 0 < t < 1; its distance is measured
+//              between the two points, |w + s u - t v|^2, not as (w . n)^2 / |n|^2.
+//   boundary   otherwise the minimum has an endpoint on one side: the four point-segment distances a0, a1 against [b0, b1] and b0, b1
+//              against [a0, a1] (segment_dist2).
+// The smallest candidate wins, ties to the earlier one in that order.  Every candidate is the distance of two points of the segments, so
+// the result is never below the true distance and never NaN for finite input; zero-length and exactly parallel edges have boundary
+// candidates only.
 // Translation units that use this are built with -ffp-contract=off: a float32 chain in numpy then reproduces every discrete decision.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -83,6 +97,62 @@ __host__ __device__ __forceinline__ TriClosest tri_closest(const float (&p)[3], 
     r.feature = t2 <= 0.f ? TRI_VERT_C : (t2 >= 1.f ? TRI_VERT_A : TRI_EDGE_CA);
 #pragma unroll
     for (int d = 0; d < 3; ++d) r.cp[d] = c[d] + t2 * (a[d] - c[d]);
+  }
+  return r;
+}
+
+enum { EE_FIRST = 0, EE_SECOND = 1, EE_INTERIOR = 2 };
+constexpr float EE_PARALLEL = 1e-13f;
+
+struct EdgeClosest {
+  float dist2;
+  float s, t;    // closest points a0 + s (a1 - a0), b0 + t (b1 - b0)
+  int category;  // uCate * 3 + vCate, EE_*
+};
+
+__host__ __device__ __forceinline__ int ee_param_category(float t) { return t <= 0.f ? EE_FIRST : (t >= 1.f ? EE_SECOND : EE_INTERIOR); }
+
+__host__ __device__ __forceinline__ EdgeClosest ee_closest(const float (&a0)[3], const float (&a1)[3], const float (&b0)[3], const float (&b1)[3]) {
+  EdgeClosest r;
+  const float u[3] = {a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]}, v[3] = {b1[0] - b0[0], b1[1] - b0[1], b1[2] - b0[2]};
+  const float w[3] = {a0[0] - b0[0], a0[1] - b0[1], a0[2] - b0[2]};
+  const float n[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+  const float nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+  const float uu = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+  bool interior = false;
+  if (nn > EE_PARALLEL * uu * vv) {
+    const float vw[3] = {v[1] * w[2] - v[2] * w[1], v[2] * w[0] - v[0] * w[2], v[0] * w[1] - v[1] * w[0]};
+    const float uw[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
+    const float s = (vw[0] * n[0] + vw[1] * n[1] + vw[2] * n[2]) / nn, t = (uw[0] * n[0] + uw[1] * n[1] + uw[2] * n[2]) / nn;
+    if (s > 0.f && s < 1.f && t > 0.f && t < 1.f) {
+      const float q[3] = {(w[0] + s * u[0]) - t * v[0], (w[1] + s * u[1]) - t * v[1], (w[2] + s * u[2]) - t * v[2]};
+      r.dist2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
+      r.s = s;
+      r.t = t;
+      r.category = EE_INTERIOR * 3 + EE_INTERIOR;
+      interior = true;
+    }
+  }
+  float p;
+  float d = segment_dist2(a0, b0, b1, p);
+  if (!interior || d < r.dist2) {
+    r.dist2 = d; r.s = 0.f; r.t = p;
+    r.category = EE_FIRST * 3 + ee_param_category(p);
+  }
+  d = segment_dist2(a1, b0, b1, p);
+  if (d < r.dist2) {
+    r.dist2 = d; r.s = 1.f; r.t = p;
+    r.category = EE_SECOND * 3 + ee_param_category(p);
+  }
+  d = segment_dist2(b0, a0, a1, p);
+  if (d < r.dist2) {
+    r.dist2 = d; r.s = p; r.t = 0.f;
+    r.category = ee_param_category(p) * 3 + EE_FIRST;
+  }
+  d = segment_dist2(b1, a0, a1, p);
+  if (d < r.dist2) {
+    r.dist2 = d; r.s = p; r.t = 1.f;
+    r.category = ee_param_category(p) * 3 + EE_SECOND;
   }
   return r;
 }

@@ -836,6 +836,27 @@ ZS_ROCM_EXPORT int zs_rocm_mesh_levelset_blocks(zs_rocm_policy *, const zs_rocm_
 ZS_ROCM_EXPORT size_t zs_rocm_mesh_levelset_select(zs_rocm_policy *, const zs_rocm_bht_3 *cand, size_t ncand, const int *keep, int *keptKeys);
 ZS_ROCM_EXPORT int zs_rocm_mesh_levelset_gather(zs_rocm_policy *, const zs_rocm_bht_3 *cand, size_t ncand, const int *keep, const float *tiles,
                                                 const zs_rocm_bht_3 *table, float *dstTiles, int numChannels);
+/* ---- mesh proximity pairs (zpc_amd/csrc/mesh_proximity.hip): the vertex-triangle (PT) and edge-edge (EE) pairs of a mesh with itself
+ * that are closer than a contact distance dHat, topological neighbours removed (a triangle that contains the vertex, two edges that share
+ * a vertex), each with its squared distance and the feature pair it is realised on -- dist_pt_sqr / pt_category_and_dist2 / dist_ee_sqr /
+ * ee_category_and_dist2 (geometry/SpatialQuery.hpp:19-500) behind iter_neighbors / self_iter_neighbors, walk and exact test in one kernel.
+ *   edges     the unique edges [ne][2] of the mesh, e[0] < e[1], in lexicographic order (from the sorted half-edge keys; an index pair
+ *             (i, i) of a degenerate triangle is no edge); zs_rocm_mesh_edges copies them to device memory
+ *   count     PT: counts[nv] by vertex; EE: counts[ne] by leaf of the edge tree (built by the first EE call, refitted by
+ *             zs_rocm_mesh_refit from then on)
+ *   fill      offsets = exclusive scan of the counts.  PT: pairs (vertex, triangle), dist2, feature (0..6 as above), bary [n][3];
+ *             EE: pairs (i, j) with i < j, dist2, category = uCate * 3 + vCate (0 first endpoint, 1 second endpoint, 2 interior; u on
+ *             edge i), st [n][2] = the parameters of the closest points on edge i and edge j.  Every output may be NULL.
+ * The order of the lists is a function of the input alone: two calls give the same bytes.  -1 and nothing written for a NULL mesh or a
+ * dHat that is not finite and positive; a mesh without triangles has zero counts. */
+ZS_ROCM_EXPORT size_t zs_rocm_mesh_num_edges(const zs_rocm_mesh *);
+ZS_ROCM_EXPORT int zs_rocm_mesh_edges(zs_rocm_policy *, const zs_rocm_mesh *, int *edges);
+ZS_ROCM_EXPORT int zs_rocm_mesh_proximity_pt_count(zs_rocm_policy *, const zs_rocm_mesh *, float dHat, int *counts);
+ZS_ROCM_EXPORT int zs_rocm_mesh_proximity_pt_fill(zs_rocm_policy *, const zs_rocm_mesh *, float dHat, const int *offsets, int *pairs, float *dist2,
+                                                  int *feature, float *bary);
+ZS_ROCM_EXPORT int zs_rocm_mesh_proximity_ee_count(zs_rocm_policy *, zs_rocm_mesh *, float dHat, int *counts);
+ZS_ROCM_EXPORT int zs_rocm_mesh_proximity_ee_fill(zs_rocm_policy *, zs_rocm_mesh *, float dHat, const int *offsets, int *pairs, float *dist2,
+                                                  int *category, float *st);
 /* ---- slotted particle storage: the motion-robust form of the fused step (zpc_amd/csrc/mpm_slotted.hip).  Storage = bins x K rounds x
  * 64 lanes in ONE TileVector<f32, 64> (slot (bin, r, lane) = element (bin K + r) 64 + lane), cellMask[bin][lane] = occupied rounds of the
  * cell; a particle is always stored under the cell of its base node, and the step keeps it so.  A particle that changes cell is finished

@@ -465,7 +465,15 @@ def _declare_containers(L):
     L.zs_rocm_mesh_levelset_select.argtypes = [vp, vp, sz, vp, vp]
     L.zs_rocm_mesh_levelset_select.restype = sz
     L.zs_rocm_mesh_levelset_gather.argtypes = [vp, vp, sz, vp, vp, vp, vp, i32]
-    for name in ("refit", "total_box", "closest_point", "signed_distance", "levelset_candidates", "levelset_blocks", "levelset_gather"):
+    L.zs_rocm_mesh_num_edges.argtypes = [vp]
+    L.zs_rocm_mesh_num_edges.restype = sz
+    L.zs_rocm_mesh_edges.argtypes = [vp, vp, vp]
+    L.zs_rocm_mesh_proximity_pt_count.argtypes = [vp, vp, f32, vp]
+    L.zs_rocm_mesh_proximity_pt_fill.argtypes = [vp, vp, f32, vp, vp, vp, vp, vp]
+    L.zs_rocm_mesh_proximity_ee_count.argtypes = [vp, vp, f32, vp]
+    L.zs_rocm_mesh_proximity_ee_fill.argtypes = [vp, vp, f32, vp, vp, vp, vp, vp]
+    for name in ("refit", "total_box", "closest_point", "signed_distance", "levelset_candidates", "levelset_blocks", "levelset_gather", "edges",
+                 "proximity_pt_count", "proximity_pt_fill", "proximity_ee_count", "proximity_ee_fill"):
         getattr(L, "zs_rocm_mesh_" + name).restype = i32
     L.zs_rocm_dof_assign.argtypes = [vp, vp, vp, sz]
     L.zs_rocm_dof_assign.restype = None

@@ -32,7 +32,9 @@ EXTRA_FLAGS = {"mpm_slotted.hip": ["-fno-slp-vectorize"], "mpm_slotblk.hip": ["-
                "levelset_transition.hip": ["-ffp-contract=off"],
                # point-triangle distances and pseudonormal signs (include/zensim_rocm/distance_device.hpp): a float32 chain in numpy
                # reproduces the discrete decisions (region, nearest triangle, sign) only without fused multiply-adds
-               "mesh.hip": ["-ffp-contract=off"]}
+               "mesh.hip": ["-ffp-contract=off"],
+               # tri_closest / ee_closest behind the proximity walks: the same chains, the same reason
+               "mesh_proximity.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst):

@@ -28,7 +28,7 @@
 
 #include "common.hpp"
 #include "bht.hpp"
-#include "../../include/zensim_rocm/mesh_device.hpp"
+#include "mesh.hpp"
 
 namespace zsr {
 
@@ -36,31 +36,6 @@ void exclusive_scan_u32(Launch &L, const unsigned *in, size_t n, unsigned *out);
 void radix_sort_pair_u32(Launch &L, const unsigned *kin, const int *vin, unsigned *kout, int *vout, size_t n, int sbit, int ebit);
 void radix_sort_pair_u64(Launch &L, const unsigned long long *kin, const int *vin, unsigned long long *kout, int *vout, size_t n, int sbit,
                          int ebit);
-
-}  // namespace zsr
-
-struct zs_rocm_mesh {
-  size_t nv = 0, nt = 0;
-  bool hasVel = false;
-  float *verts = nullptr, *vel = nullptr, *faceN = nullptr, *vertN = nullptr, *edgeN = nullptr, *angles = nullptr, *boxes = nullptr;
-  int *tris = nullptr, *heVals = nullptr, *cornerVals = nullptr, *stats = nullptr;
-  unsigned long long *heKeys = nullptr;  // sorted half-edge keys (min vertex << 32 | max vertex), heVals = 3 t + edge
-  unsigned *cornerKeys = nullptr;        // sorted corner keys (vertex), cornerVals = 3 t + corner
-  zs_rocm_lbvh *bvh = nullptr;
-  zsr::TriMeshDev dev() const {
-    zsr::TriMeshDev d;
-    d.verts = verts; d.tris = tris; d.vel = hasVel ? vel : nullptr;
-    d.faceNormals = faceN; d.vertNormals = vertN; d.edgeNormals = edgeN;
-    zs_rocm_lbvh_view v;
-    zs_rocm_lbvh_get_view(bvh, &v);
-    d.bvh.orderedBvs = (const zsr::AABB3 *)v.orderedBvs; d.bvh.parents = v.parents; d.bvh.levels = v.levels; d.bvh.leafInds = v.leafInds;
-    d.bvh.auxIndices = v.auxIndices; d.bvh.numNodes = v.numNodes;
-    d.numVerts = (int)nv; d.numTris = (int)nt;
-    return d;
-  }
-};
-
-namespace zsr {
 
 constexpr int MESH_STAGE_TRIS = 640, MESH_STAGE_STRIDE = 12, MESH_QUEUE = 1024;
 constexpr int MESH_LS_SIDE = 8, MESH_LS_BLOCK = 512;
@@ -450,6 +425,39 @@ static void mesh_pseudonormals(Launch &L, zs_rocm_mesh &m) {
 
 static bool mesh_ok(const zs_rocm_mesh *m) { return m && m->bvh && m->stats; }
 
+// the unique edges from the sorted half-edge keys: the first key of every run, keys with min == max dropped; lexicographic order
+__global__ __launch_bounds__(256) void mesh_edge_flags_kernel(const unsigned long long *keys, size_t n3, unsigned *flags) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n3) return;
+  unsigned f = 0;
+  if (i < n3) {
+    const unsigned long long k = keys[i];
+    f = (i == 0 || keys[i - 1] != k) && (unsigned)(k >> 32) != (unsigned)k ? 1u : 0u;
+  }
+  flags[i] = f;  // (flags[n3] = 0: the scan's last entry is the number of edges)
+}
+__global__ __launch_bounds__(256) void mesh_edge_compact_kernel(const unsigned long long *keys, size_t n3, const unsigned *flags,
+                                                                const unsigned *offsets, int *edges) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n3 || !flags[i]) return;
+  const unsigned long long k = keys[i];
+  edges[2 * (size_t)offsets[i]] = (int)(unsigned)(k >> 32);
+  edges[2 * (size_t)offsets[i] + 1] = (int)(unsigned)k;
+}
+static void mesh_edges(Launch &L, zs_rocm_mesh &m) {
+  const size_t n3 = 3 * m.nt;
+  unsigned *flags = (unsigned *)L.temp(sizeof(unsigned) * (n3 + 1)), *offsets = (unsigned *)L.temp(sizeof(unsigned) * (n3 + 1));
+  hipLaunchKernelGGL(mesh_edge_flags_kernel, dim3(ceil_div(n3 + 1, 256)), dim3(256), 0, L.stream, m.heKeys, n3, flags);
+  exclusive_scan_u32(L, flags, n3 + 1, offsets);
+  unsigned ne = 0;
+  ZSR_CHECK(hipMemcpyAsync(&ne, offsets + n3, sizeof(unsigned), hipMemcpyDeviceToHost, L.stream));
+  ZSR_CHECK(hipStreamSynchronize(L.stream));
+  m.ne = ne;
+  ZSR_CHECK(hipMalloc((void **)&m.edges, sizeof(int) * 2 * (ne ? ne : 1)));
+  if (ne) hipLaunchKernelGGL(mesh_edge_compact_kernel, dim3(ceil_div(n3, 256)), dim3(256), 0, L.stream, m.heKeys, n3, flags, offsets, m.edges);
+}
+
+
 static MeshLsFrame ls_frame(const float *origin, float voxel, float band) {
   MeshLsFrame f;
   f.o[0] = origin[0]; f.o[1] = origin[1]; f.o[2] = origin[2];
@@ -528,6 +536,7 @@ zs_rocm_mesh *zs_rocm_mesh_create(zs_rocm_policy *pol, const float *verts, size_
       const int vb = bits_for(nv);
       radix_sort_pair_u64(L, hk, ids, m->heKeys, m->heVals, n3, 0, 32 + vb);
       radix_sort_pair_u32(L, ck, ids, m->cornerKeys, m->cornerVals, n3, 0, vb);
+      mesh_edges(L, *m);
     }
     mesh_pseudonormals(L, *m);
   }
@@ -539,7 +548,10 @@ void zs_rocm_mesh_destroy(zs_rocm_mesh *m) {
   (void)hipFree(m->verts); (void)hipFree(m->vel); (void)hipFree(m->vertN); (void)hipFree(m->tris); (void)hipFree(m->faceN);
   (void)hipFree(m->angles); (void)hipFree(m->edgeN); (void)hipFree(m->boxes); (void)hipFree(m->heKeys); (void)hipFree(m->heVals);
   (void)hipFree(m->cornerKeys); (void)hipFree(m->cornerVals); (void)hipFree(m->stats);
+  (void)hipFree(m->edges); (void)hipFree(m->edgeBoxes); (void)hipFree(m->triPacked); (void)hipFree(m->edgePacked);
+  (void)hipFree(m->ptCache); (void)hipFree(m->ptCacheCounts); (void)hipFree(m->eeCache); (void)hipFree(m->eeCacheCounts);
   zs_rocm_lbvh_destroy(m->bvh);
+  if (m->edgeBvh) zs_rocm_lbvh_destroy(m->edgeBvh);
   delete m;
 }
 
@@ -555,6 +567,7 @@ int zs_rocm_mesh_refit(zs_rocm_policy *pol, zs_rocm_mesh *m, const float *verts,
     mesh_faces(L, *m);
   }
   if (m->nt && zs_rocm_lbvh_refit(pol, m->bvh, m->boxes, m->nt) != 0) return -1;
+  if (mesh_proximity_refit(pol, *m) != 0) return -1;
   Launch L(pol, "mesh_refit (pseudonormals)");
   mesh_pseudonormals(L, *m);
   return 0;

@@ -1,5 +1,6 @@
 """Triangle meshes as colliders: TriMesh owns a device mesh object of the library (LBvh over the triangle boxes, face normals, vertex and
-edge pseudonormals) and answers closest-point and signed-distance queries; SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
+edge pseudonormals) and answers closest-point and signed-distance queries and the proximity pairs of the mesh with itself (vertex-triangle and edge-edge within a
+contact distance); SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
 into a sparse level set.  Set-up code: torch for the plumbing; every query runs in the library's HIP kernels."""
 import ctypes as C
 
@@ -8,6 +9,8 @@ import numpy as np
 from ._lib import lib, MeshView
 
 FEATURES = ("vertex a", "vertex b", "vertex c", "edge ab", "edge bc", "edge ca", "face")
+# ee_category = uCate * 3 + vCate of the closest points a0 + s (a1 - a0), b0 + t (b1 - b0) of two edges
+EE_CATEGORIES = ("a0 - b0", "a0 - b1", "a0 - edge b", "a1 - b0", "a1 - b1", "a1 - edge b", "edge a - b0", "edge a - b1", "edge a - edge b")
 STAT_NAMES = ("boundary_edges", "nonmanifold_edges", "inconsistent_edges", "zero_area_triangles", "bad_indices")
 FLT_MAX = float(np.finfo(np.float32).max)
 
@@ -34,6 +37,17 @@ def _dev_f32(a, cols):
     if t.ndim != 2 or t.shape[1] != cols:
         raise ValueError("expected an [n, %d] array" % cols)
     return t
+
+
+class Proximity:
+    """result of TriMesh.proximity: device tensors, None for a side that was not asked for.  pt_pairs [n, 2] (vertex, triangle), pt_dist2 [n],
+    pt_feature [n] (FEATURES), pt_bary [n, 3]; ee_pairs [m, 2] (edge i < edge j, rows of TriMesh.edges()), ee_dist2 [m], ee_category [m]
+    (EE_CATEGORIES), ee_st [m, 2] (the parameters of the closest points on edge i and edge j)"""
+    __slots__ = ("pt_pairs", "pt_dist2", "pt_feature", "pt_bary", "ee_pairs", "ee_dist2", "ee_category", "ee_st")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
 
 
 class TriMesh:
@@ -100,6 +114,56 @@ class TriMesh:
             raise RuntimeError("zs_rocm_mesh_refit failed")
         self.pol.syncCtx()
         self.has_velocity = self.has_velocity or w is not None
+
+    @property
+    def num_edges(self):
+        return int(lib().zs_rocm_mesh_num_edges(self._h))
+
+    def edges(self):
+        """the unique edges [ne, 2] int32 on the device, e[0] < e[1], in lexicographic order"""
+        import torch
+        e = torch.empty(self.num_edges, 2, dtype=torch.int32, device="cuda")
+        if lib().zs_rocm_mesh_edges(self.pol.handle, self._h, e.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mesh_edges failed")
+        self.pol.syncCtx()
+        return e
+
+    def _pairs(self, n, count, fill, dhat, widths):
+        """count -> exclusive scan -> one read-back of the total -> fill; returns (pairs, dist2, int tag, float coordinates)"""
+        import torch
+        from .primitives import exclusive_scan
+        counts = torch.zeros(n + 1, dtype=torch.int32, device="cuda")   # one more: its offset is the total
+        if count(self.pol.handle, self._h, dhat, counts.data_ptr()) != 0:
+            raise RuntimeError("the proximity count pass failed")
+        offsets = torch.empty_like(counts)
+        exclusive_scan(self.pol, counts, offsets)
+        self.pol.syncCtx()
+        total = int(offsets[n].item())
+        pairs = torch.empty(total, 2, dtype=torch.int32, device="cuda")
+        dist2 = torch.empty(total, dtype=torch.float32, device="cuda")
+        tag = torch.empty(total, dtype=torch.int32, device="cuda")
+        coord = torch.empty(total, widths, dtype=torch.float32, device="cuda")
+        if total and fill(self.pol.handle, self._h, dhat, offsets.data_ptr(), pairs.data_ptr(), dist2.data_ptr(), tag.data_ptr(),
+                          coord.data_ptr()) != 0:
+            raise RuntimeError("the proximity fill pass failed")
+        self.pol.syncCtx()
+        return pairs, dist2, tag, coord
+
+    def proximity(self, dhat, pt=True, ee=True):
+        """the vertex-triangle and edge-edge pairs of the mesh with itself closer than dhat, without topological neighbours (a triangle
+        that contains the vertex, edges that share a vertex): a Proximity.  The lists are in a fixed order: two calls give the same bytes."""
+        dhat = float(dhat)
+        if not (np.isfinite(dhat) and dhat > 0 and np.float32(dhat) > 0 and np.isfinite(np.float32(dhat))):
+            raise ValueError("TriMesh.proximity: dhat must be finite and positive")
+        r = Proximity()
+        L = lib()
+        if pt:
+            r.pt_pairs, r.pt_dist2, r.pt_feature, r.pt_bary = self._pairs(self.nv, L.zs_rocm_mesh_proximity_pt_count,
+                                                                          L.zs_rocm_mesh_proximity_pt_fill, dhat, 3)
+        if ee:
+            r.ee_pairs, r.ee_dist2, r.ee_category, r.ee_st = self._pairs(self.num_edges, L.zs_rocm_mesh_proximity_ee_count,
+                                                                         L.zs_rocm_mesh_proximity_ee_fill, dhat, 2)
+        return r
 
     @staticmethod
     def _cap(cap):
