@@ -857,6 +857,35 @@ ZS_ROCM_EXPORT int zs_rocm_mesh_proximity_pt_fill(zs_rocm_policy *, const zs_roc
 ZS_ROCM_EXPORT int zs_rocm_mesh_proximity_ee_count(zs_rocm_policy *, zs_rocm_mesh *, float dHat, int *counts);
 ZS_ROCM_EXPORT int zs_rocm_mesh_proximity_ee_fill(zs_rocm_policy *, zs_rocm_mesh *, float dHat, const int *offsets, int *pairs, float *dist2,
                                                   int *category, float *st);
+/* ---- mesh barrier potential (zpc_amd/csrc/mesh_barrier.hip, include/zensim_rocm/barrier_device.hpp): the IPC log-barrier contact energy
+ * and its gradient (the contact force) over the PT and EE pair lists of the proximity passes -- barrier / barrier_gradient
+ * (geometry/SpatialQuery.hpp:502-531) with dist_grad_* and mollifier_ee (geometry/Distance.hpp) -- at the mesh's own positions or at trial
+ * positions verts [nv][3] on the same topology (NULL: the mesh's own).  Distance, parameters and feature are recomputed at those positions;
+ * a pair at dHat or beyond contributes exactly zero.  b(d2) = -kappa (d2 - dHat^2)^2 log(d2 / dHat^2); an EE pair is multiplied by the
+ * mollifier of its edges' cross product against 1e-2 restLen2_i restLen2_j when mollify != 0.
+ *   set_rest    stores the squared rest length of every unique edge [ne] in the mesh object, from verts [nv][3] or (NULL) the mesh's current
+ *               vertices; zs_rocm_mesh_rest copies them out ([ne], -1 before set_rest)
+ *   sizes       sizes[0] = ints of starts (nv + 1), sizes[1] = ints of entries (4 (npt + nee)), sizes[2] = floats of scratch (12 (npt + nee))
+ *   incidence   starts / entries of a pair of lists: entries = the (pair, corner) numbers 4 pair + corner (EE pairs numbered behind the PT
+ *               pairs) sorted by vertex, list order inside a vertex; starts[v] .. starts[v + 1] is the run of vertex v.  Depends on the
+ *               lists alone, not on positions: build once, reuse for every call on the same lists.
+ *   energy      ptEnergy [npt], eeEnergy [nee] (float), total (one double, PT then EE, summed in a fixed order), status int[2] = the PT and EE
+ *               pairs at zero distance (their energy is +inf, they add nothing to the gradient).  Every output may be NULL.
+ *   gradient    the same and grad [nv][3], fully overwritten, zero for a vertex in no pair; scratch holds the per-pair contributions.
+ * Two calls on the same input give the same bytes (no float atomics).  -1 and nothing written for a NULL mesh, a dHat or kappa that is not
+ * finite and positive, mollify != 0 before set_rest, or 2^28 pairs and more; empty lists give zero energy and a zero gradient. */
+ZS_ROCM_EXPORT int zs_rocm_mesh_set_rest(zs_rocm_policy *, zs_rocm_mesh *, const float *verts);
+ZS_ROCM_EXPORT int zs_rocm_mesh_rest(zs_rocm_policy *, const zs_rocm_mesh *, float *restLen2);
+ZS_ROCM_EXPORT int zs_rocm_mesh_barrier_sizes(const zs_rocm_mesh *, size_t npt, size_t nee, size_t *sizes);
+ZS_ROCM_EXPORT int zs_rocm_mesh_barrier_incidence(zs_rocm_policy *, const zs_rocm_mesh *, const int *ptPairs, size_t npt, const int *eePairs,
+                                                  size_t nee, int *starts, int *entries);
+ZS_ROCM_EXPORT int zs_rocm_mesh_barrier_energy(zs_rocm_policy *, const zs_rocm_mesh *, const float *verts, const int *ptPairs, size_t npt,
+                                               const int *eePairs, size_t nee, float dHat, float kappa, int mollify, float *ptEnergy,
+                                               float *eeEnergy, double *total, int *status);
+ZS_ROCM_EXPORT int zs_rocm_mesh_barrier_gradient(zs_rocm_policy *, const zs_rocm_mesh *, const float *verts, const int *ptPairs, size_t npt,
+                                                 const int *eePairs, size_t nee, float dHat, float kappa, int mollify, const int *starts,
+                                                 const int *entries, float *scratch, float *ptEnergy, float *eeEnergy, double *total,
+                                                 float *grad, int *status);
 /* ---- slotted particle storage: the motion-robust form of the fused step (zpc_amd/csrc/mpm_slotted.hip).  Storage = bins x K rounds x
  * 64 lanes in ONE TileVector<f32, 64> (slot (bin, r, lane) = element (bin K + r) 64 + lane), cellMask[bin][lane] = occupied rounds of the
  * cell; a particle is always stored under the cell of its base node, and the step keeps it so.  A particle that changes cell is finished

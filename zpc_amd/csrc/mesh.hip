@@ -550,6 +550,7 @@ void zs_rocm_mesh_destroy(zs_rocm_mesh *m) {
   (void)hipFree(m->cornerKeys); (void)hipFree(m->cornerVals); (void)hipFree(m->stats);
   (void)hipFree(m->edges); (void)hipFree(m->edgeBoxes); (void)hipFree(m->triPacked); (void)hipFree(m->edgePacked);
   (void)hipFree(m->ptCache); (void)hipFree(m->ptCacheCounts); (void)hipFree(m->eeCache); (void)hipFree(m->eeCacheCounts);
+  (void)hipFree(m->restLen2);
   zs_rocm_lbvh_destroy(m->bvh);
   if (m->edgeBvh) zs_rocm_lbvh_destroy(m->edgeBvh);
   delete m;

@@ -1,5 +1,5 @@
-// mesh.hpp -- the triangle-mesh object of the C ABI, shared by mesh.hip (colliders, mesh -> level set) and mesh_proximity.hip (the
-// point-triangle and edge-edge pairs within a contact distance).
+// mesh.hpp -- the triangle-mesh object of the C ABI, shared by mesh.hip (colliders, mesh -> level set), mesh_proximity.hip (the
+// point-triangle and edge-edge pairs within a contact distance) and mesh_barrier.hip (the contact potential on those pairs).
 #pragma once
 #include "common.hpp"
 #include "../../include/zensim_rocm/mesh_device.hpp"
@@ -35,6 +35,9 @@ struct zs_rocm_mesh {
   float eeCacheDHat = 0.f;
   mutable bool ptCacheValid = false;
   bool eeCacheValid = false;
+  // the squared rest length of every unique edge (mesh_barrier.hip: the threshold of the edge-edge mollifier), set by zs_rocm_mesh_set_rest
+  float *restLen2 = nullptr;
+  bool hasRest = false;
   zsr::TriMeshDev dev() const {
     zsr::TriMeshDev d;
     d.verts = verts; d.tris = tris; d.vel = hasVel ? vel : nullptr;

@@ -1,6 +1,6 @@
 """Triangle meshes as colliders: TriMesh owns a device mesh object of the library (LBvh over the triangle boxes, face normals, vertex and
 edge pseudonormals) and answers closest-point and signed-distance queries and the proximity pairs of the mesh with itself (vertex-triangle and edge-edge within a
-contact distance); SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
+contact distance) and the IPC barrier potential with its gradient on those pairs; SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
 into a sparse level set.  Set-up code: torch for the plumbing; every query runs in the library's HIP kernels."""
 import ctypes as C
 
@@ -39,7 +39,11 @@ def _dev_f32(a, cols):
     return t
 
 
-class Proximity:
+class _ProximityState:
+    """room on a Proximity for what the library keeps with it (the incidence of TriMesh.barrier), next to its public fields"""
+
+
+class Proximity(_ProximityState):
     """result of TriMesh.proximity: device tensors, None for a side that was not asked for.  pt_pairs [n, 2] (vertex, triangle), pt_dist2 [n],
     pt_feature [n] (FEATURES), pt_bary [n, 3]; ee_pairs [m, 2] (edge i < edge j, rows of TriMesh.edges()), ee_dist2 [m], ee_category [m]
     (EE_CATEGORIES), ee_st [m, 2] (the parameters of the closest points on edge i and edge j)"""
@@ -48,6 +52,14 @@ class Proximity:
     def __init__(self):
         for k in self.__slots__:
             setattr(self, k, None)
+        self._incidence = None      # (starts, entries, scratch size) of TriMesh.barrier, built by its first gradient call
+
+
+class Barrier:
+    """result of TriMesh.barrier: energy (float64 device scalar: PT then EE, summed in a fixed order), pt_energy [npt], ee_energy [nee]
+    (None for a side the Proximity does not have), grad [nv, 3] or None, zero_distance = (PT, EE) pairs at zero distance (their energy is
+    +inf and they add nothing to the gradient)"""
+    __slots__ = ("energy", "pt_energy", "ee_energy", "grad", "zero_distance")
 
 
 class TriMesh:
@@ -163,6 +175,87 @@ class TriMesh:
         if ee:
             r.ee_pairs, r.ee_dist2, r.ee_category, r.ee_st = self._pairs(self.num_edges, L.zs_rocm_mesh_proximity_ee_count,
                                                                          L.zs_rocm_mesh_proximity_ee_fill, dhat, 2)
+        return r
+
+    def set_rest(self, verts=None):
+        """stores the squared rest length of every unique edge (the threshold of the edge-edge mollifier) from verts [nv, 3], or from the
+        mesh's current vertices"""
+        v = None if verts is None else _dev_f32(verts, 3)
+        if v is not None and v.shape[0] != self.nv:
+            raise ValueError("TriMesh.set_rest: [nv, 3] positions on the same topology")
+        if lib().zs_rocm_mesh_set_rest(self.pol.handle, self._h, None if v is None else v.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mesh_set_rest failed")
+        self.pol.syncCtx()
+        self.has_rest = True
+
+    def rest(self):
+        """the squared rest lengths [ne] float32 on the device, rows as TriMesh.edges()"""
+        import torch
+        r = torch.empty(self.num_edges, dtype=torch.float32, device="cuda")
+        if lib().zs_rocm_mesh_rest(self.pol.handle, self._h, r.data_ptr()) != 0:
+            raise ValueError("TriMesh.rest: call set_rest first")
+        self.pol.syncCtx()
+        return r
+
+    def _incidence(self, prox, pt, ee):
+        """(starts, entries, scratch size) of the lists of prox, built once and kept on prox"""
+        import torch
+        if getattr(prox, "_incidence", None) is None:
+            npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+            sizes = (C.c_size_t * 3)()
+            if lib().zs_rocm_mesh_barrier_sizes(self._h, npt, nee, sizes) != 0:
+                raise ValueError("TriMesh.barrier: too many pairs")
+            starts = torch.empty(sizes[0], dtype=torch.int32, device="cuda")
+            entries = torch.empty(sizes[1], dtype=torch.int32, device="cuda")
+            if lib().zs_rocm_mesh_barrier_incidence(self.pol.handle, self._h, None if pt is None else pt.data_ptr(), npt,
+                                                    None if ee is None else ee.data_ptr(), nee, starts.data_ptr(), entries.data_ptr()) != 0:
+                raise RuntimeError("zs_rocm_mesh_barrier_incidence failed")
+            self.pol.syncCtx()
+            prox._incidence = (starts, entries, int(sizes[2]))
+        return prox._incidence
+
+    def barrier(self, prox, dhat, kappa, verts=None, mollify=True, gradient=True):
+        """the IPC barrier potential -kappa (d2 - dhat^2)^2 log(d2 / dhat^2) summed over the pairs of prox (a Proximity of this mesh; a side
+        that is None is skipped), and its gradient: a Barrier.  verts [nv, 3]: trial positions on the same topology instead of the mesh's
+        own; distances are recomputed there, the lists stay as they are.  mollify: edge-edge pairs are multiplied by the mollifier of
+        nearly parallel edges, which needs set_rest.  Two calls give the same bytes."""
+        import torch
+        dhat, kappa = float(dhat), float(kappa)
+        for name, x in (("dhat", dhat), ("kappa", kappa)):
+            if not (np.isfinite(x) and x > 0 and np.float32(x) > 0 and np.isfinite(np.float32(x))):
+                raise ValueError("TriMesh.barrier: %s must be finite and positive" % name)
+        if mollify and not getattr(self, "has_rest", False):
+            raise ValueError("TriMesh.barrier: mollify=True needs the rest lengths, call set_rest first")
+        if not isinstance(prox, Proximity):
+            raise ValueError("TriMesh.barrier: prox is the result of TriMesh.proximity")
+        v = None if verts is None else _dev_f32(verts, 3)
+        if v is not None and v.shape[0] != self.nv:
+            raise ValueError("TriMesh.barrier: verts are [nv, 3] positions on the same topology")
+        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
+        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
+        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+        r = Barrier()
+        r.energy = torch.empty((), dtype=torch.float64, device="cuda")
+        r.pt_energy = None if pt is None else torch.empty(npt, dtype=torch.float32, device="cuda")
+        r.ee_energy = None if ee is None else torch.empty(nee, dtype=torch.float32, device="cuda")
+        r.grad = None
+        status = torch.empty(2, dtype=torch.int32, device="cuda")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        head = (self.pol.handle, self._h, ptr(v), ptr(pt), npt, ptr(ee), nee, dhat, kappa, 1 if mollify else 0)
+        tail = (ptr(r.pt_energy), ptr(r.ee_energy), r.energy.data_ptr())
+        if gradient:
+            starts, entries, nscratch = self._incidence(prox, pt, ee)
+            scratch = torch.empty(nscratch, dtype=torch.float32, device="cuda")
+            r.grad = torch.empty(self.nv, 3, dtype=torch.float32, device="cuda")
+            rc = lib().zs_rocm_mesh_barrier_gradient(*head, starts.data_ptr(), entries.data_ptr(), scratch.data_ptr(), *tail, r.grad.data_ptr(),
+                                                     status.data_ptr())
+        else:
+            rc = lib().zs_rocm_mesh_barrier_energy(*head, *tail, status.data_ptr())
+        if rc != 0:
+            raise RuntimeError("the barrier call failed")
+        self.pol.syncCtx()
+        z = status.tolist()
+        r.zero_distance = (int(z[0]), int(z[1]))
         return r
 
     @staticmethod
