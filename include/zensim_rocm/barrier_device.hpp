@@ -21,6 +21,30 @@
 //              eps = 0 (unmollified, or an edge of zero rest length; also an eps below the smallest normal float): m = 1.
 //   zero       d2 == 0 (or d2 / dHat2 underflowing to 0, or a b' beyond the float range): energy +inf, no gradient, status BARRIER_ZERO for the
 //              caller to count.  Nothing else divides by d2 and 2 / eps is finite, so no NaN reaches the gradient from finite coordinates.
+//   hessian    matrix-free: barrier_pt_hvp / barrier_ee_hvp return (H_pair x) on the four corners for a direction x, never the 12 x 12 block.
+//              d2 = min over lambda of |r(x, lambda)|^2, r = sum_k w_k(lambda) x_k.  The envelope argument one order up: a clamped parameter
+//              is a constant, a free one solves df/dlambda_j = 0, and differentiating that condition gives dlambda/dx = -A^-1 F:
+//                  (hess d2 . v)_k = 2 w_k (W v) - (F^T A^-1 F v)_k,   W v = sum_k w_k v_k
+//                  r_j = dr/dlambda_j = sum_k (dw_k/dlambda_j) x_k                    (an edge vector up to sign)
+//                  A_ij = 2 r_i . r_j,   (F v)_j = 2 (r_j . (W v) + r . sum_k (dw_k/dlambda_j) v_k)
+//                  (F^T y)_k = 2 sum_j y_j (w_k r_j + (dw_k/dlambda_j) r)
+//              The free parameters follow from the feature tri_closest / ee_closest return: the face has two (bary1, bary2), an edge
+//              region one, a vertex region none; an edge pair one per side that is EE_INTERIOR.  No per-feature formulas: the feature
+//              only selects the rows dw/dlambda.  With two free parameters det A = 4 |r_1 x r_2|^2 is taken from the cross product, not
+//              from |r_1|^2 |r_2|^2 - (r_1 . r_2)^2, which cancels in float32.  A degenerate free system (det A, or the single A_11, not
+//              above zero) falls back to the clamped form: the term F^T A^-1 F is dropped.
+//              barrier: with g = grad d2:  H_b v = b'' (g . v) g + b' (hess d2 . v),
+//                  b''(d2) = kappa (-2 log(d2 / dHat2) - 4 t / d2 + t^2 / d2^2)
+//              mollified EE, E = m(c) b(d2):  H v = m H_b v + m' b' ((grad c . v) g + (g . v) grad c) + b (m'' (grad c . v) grad c + m' (hess c . v)),
+//                  m'' = -2 / eps^2 for c < eps, else 0;  dn = du x v + u x dv, du = v_1 - v_0, dv = v_3 - v_2;
+//                  (hess c . v) = 2 (dv x n + v x dn) on the u side, 2 (dn x u + n x du) on the v side, signs (-, +, -, +) as for grad c.
+//              Exactly parallel edges: m = 0 and grad c = 0, what is left is b m' hess c . v, which does not depend on (s, t).
+//   psd        PSD = true: every indefinite term is discarded analytically, no eigen-decomposition:
+//                  H+_b v = b'' (g . v) g + |b'| F^T A^-1 F v          (b'' > 0, b' < 0 on (0, dHat2), A positive definite)
+//                  H+ v   = m H+_b v + b m' 2 J^T J v,  J = dn/dx:  2 v x dn on the u side, 2 dn x u on the v side
+//              positive semi-definite by construction, and without the mollifier H+ - H = 2 |b'| W^T W: H+ majorises H.  This is not the
+//              eigenvalue projection of the 12 x 12 block.
+//   zero (hvp) as for the gradient; also a b'' or a product beyond the float range: status BARRIER_ZERO, the pair contributes exactly zero.
 // Float32 throughout; the logarithm is the platform's logf.  Translation units that use this are built with -ffp-contract=off, as for
 // distance_device.hpp: a float32 chain in numpy then reproduces it operation by operation.
 #pragma once
@@ -115,6 +139,190 @@ __host__ __device__ __forceinline__ int barrier_ee(const float (&a0)[3], const f
     }
   }
   return status;
+}
+
+// b, b' and b'' at d2: barrier_eval, and ZERO as well when b'' leaves the float range (then b = +inf, b' = b'' = 0)
+__host__ __device__ __forceinline__ int barrier_eval2(float d2, float dHat2, float kappa, float &b, float &bp, float &bpp) {
+  bpp = 0.f;
+  const int status = barrier_eval(d2, dHat2, kappa, b, bp);
+  if (status != BARRIER_ACTIVE) return status;
+  const float t = d2 - dHat2, lg = logf(d2 / dHat2), q = t / d2;
+  const float dd = kappa * ((-2.f * lg - 4.f * q) + q * q);
+  if (!(fabsf(dd) <= FLT_MAX)) {
+    b = INFINITY;
+    bp = 0.f;
+    return BARRIER_ZERO;
+  }
+  bpp = dd;
+  return status;
+}
+
+__host__ __device__ __forceinline__ float barrier_dot(const float (&a)[3], const float (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+__host__ __device__ __forceinline__ void barrier_cross(const float (&a)[3], const float (&b)[3], float (&c)[3]) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// H_b x (PSD: H+_b x) on the four corners from the weights w, r = P - Q and up to two free parameters: f1 / f2 say whether slot 1 / 2 is
+// free, d1 / d2 are its rows dw/dlambda, r1 / r2 its vectors dr/dlambda (all zero for a slot that is not free).  Returns g . x.
+template <bool PSD>
+__host__ __device__ __forceinline__ float barrier_hvp_core(const float (&w)[4], const float (&r)[3], bool f1, bool f2, const float (&d1)[4],
+                                                           const float (&d2)[4], const float (&r1)[3], const float (&r2)[3],
+                                                           const float (&x)[4][3], float bp, float bpp, float (&h)[4][3]) {
+  float Wx[3], D1[3], D2[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    Wx[d] = w[0] * x[0][d] + w[1] * x[1][d] + w[2] * x[2][d] + w[3] * x[3][d];
+    D1[d] = d1[0] * x[0][d] + d1[1] * x[1][d] + d1[2] * x[2][d] + d1[3] * x[3][d];
+    D2[d] = d2[0] * x[0][d] + d2[1] * x[1][d] + d2[2] * x[2][d] + d2[3] * x[3][d];
+  }
+  const float gx = 2.f * barrier_dot(r, Wx);
+  const float F1 = 2.f * (barrier_dot(r1, Wx) + barrier_dot(r, D1)), F2 = 2.f * (barrier_dot(r2, Wx) + barrier_dot(r, D2));
+  const float A11 = 2.f * barrier_dot(r1, r1), A22 = 2.f * barrier_dot(r2, r2), A12 = 2.f * barrier_dot(r1, r2);
+  float y1 = 0.f, y2 = 0.f;
+  if (f1 && f2) {
+    float c12[3];
+    barrier_cross(r1, r2, c12);
+    const float det = 4.f * barrier_dot(c12, c12);
+    if (det > 0.f) {
+      y1 = (A22 * F1 - A12 * F2) / det;
+      y2 = (A11 * F2 - A12 * F1) / det;
+    }
+  } else if (f1) {
+    if (A11 > 0.f) y1 = F1 / A11;
+  } else if (f2) {
+    if (A22 > 0.f) y2 = F2 / A22;
+  }
+  const float cg = bpp * gx, abp = fabsf(bp);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float gk = (2.f * w[k]) * r[d];
+      const float ft = 2.f * (y1 * (w[k] * r1[d] + d1[k] * r[d]) + y2 * (w[k] * r2[d] + d2[k] * r[d]));
+      h[k][d] = PSD ? cg * gk + abp * ft : cg * gk + bp * ((2.f * w[k]) * Wx[d] - ft);
+    }
+  return gx;
+}
+
+// a product beyond the float range (or a NaN out of inf - inf on the way): the pair counts as ZERO and contributes nothing
+__host__ __device__ __forceinline__ int barrier_hvp_finish(float (&h)[4][3]) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) ok = ok && fabsf(h[k][d]) <= FLT_MAX;
+  if (ok) return BARRIER_ACTIVE;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h[k][0] = h[k][1] = h[k][2] = 0.f;
+  return BARRIER_ZERO;
+}
+
+// h[k] = (H x)_k on (p, a, b, c) of a point-triangle pair for the direction x[k] at those vertices; PSD: the H+ of the header; returns BARRIER_*
+template <bool PSD>
+__host__ __device__ __forceinline__ int barrier_pt_hvp(const float (&p)[3], const float (&a)[3], const float (&b)[3], const float (&c)[3],
+                                                       const float (&x)[4][3], float dHat2, float kappa, float (&h)[4][3]) {
+  const TriClosest cl = tri_closest(p, a, b, c);
+  float bb, bp, bpp;
+  const int status = barrier_eval2(cl.dist2, dHat2, kappa, bb, bp, bpp);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h[k][0] = h[k][1] = h[k][2] = 0.f;
+  if (status != BARRIER_ACTIVE) return status;
+  const int ft = cl.feature;
+  const bool face = ft == TRI_FACE, eab = ft == TRI_EDGE_AB, ebc = ft == TRI_EDGE_BC, eca = ft == TRI_EDGE_CA;
+  // slot 1: bary1 of the face or the parameter of the edge region, slot 2: bary2 of the face
+  const float d1[4] = {0.f, (face || eab) ? 1.f : (eca ? -1.f : 0.f), (face || eab) ? -1.f : (ebc ? 1.f : 0.f), ebc ? -1.f : (eca ? 1.f : 0.f)};
+  const float d2[4] = {0.f, face ? 1.f : 0.f, 0.f, face ? -1.f : 0.f};
+  const float w[4] = {1.f, -cl.bary[0], -cl.bary[1], -cl.bary[2]};
+  float r[3], r1[3], r2[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    r[d] = p[d] - cl.cp[d];
+    r1[d] = (face || eab) ? a[d] - b[d] : (ebc ? b[d] - c[d] : (eca ? c[d] - a[d] : 0.f));
+    r2[d] = face ? a[d] - c[d] : 0.f;
+  }
+  barrier_hvp_core<PSD>(w, r, face || eab || ebc || eca, face, d1, d2, r1, r2, x, bp, bpp, h);
+  return barrier_hvp_finish(h);
+}
+
+// the same on (a0, a1, b0, b1) of an edge-edge pair; eps: barrier_ee_eps, 0 = unmollified
+template <bool PSD>
+__host__ __device__ __forceinline__ int barrier_ee_hvp(const float (&a0)[3], const float (&a1)[3], const float (&b0)[3], const float (&b1)[3],
+                                                       const float (&x)[4][3], float dHat2, float kappa, float eps, float (&h)[4][3]) {
+  const EdgeClosest cl = ee_closest(a0, a1, b0, b1);
+  float bb, bp, bpp;
+  const int status = barrier_eval2(cl.dist2, dHat2, kappa, bb, bp, bpp);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h[k][0] = h[k][1] = h[k][2] = 0.f;
+  if (status != BARRIER_ACTIVE) return status;
+  const bool fs = cl.category / 3 == EE_INTERIOR, ft = cl.category % 3 == EE_INTERIOR;
+  const float u[3] = {a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]}, v[3] = {b1[0] - b0[0], b1[1] - b0[1], b1[2] - b0[2]};
+  const float d1[4] = {fs ? -1.f : 0.f, fs ? 1.f : 0.f, 0.f, 0.f}, d2[4] = {0.f, 0.f, ft ? 1.f : 0.f, ft ? -1.f : 0.f};
+  const float w[4] = {1.f - cl.s, cl.s, -(1.f - cl.t), -cl.t};
+  float r[3], r1[3], r2[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    r[d] = (a0[d] + cl.s * u[d]) - (b0[d] + cl.t * v[d]);
+    r1[d] = fs ? u[d] : 0.f;
+    r2[d] = ft ? b0[d] - b1[d] : 0.f;
+  }
+  float hb[4][3];
+  const float gx = barrier_hvp_core<PSD>(w, r, fs, ft, d1, d2, r1, r2, x, bp, bpp, hb);
+  float n[3];
+  barrier_cross(u, v, n);
+  const float c = barrier_dot(n, n);
+  float m = 1.f, mp = 0.f;
+  const bool on = eps >= FLT_MIN && c < eps;
+  if (on) {
+    const float xx = c / eps;
+    m = (2.f - xx) * xx;
+    mp = (2.f / eps) * (1.f - xx);
+  }
+  const float du[3] = {x[1][0] - x[0][0], x[1][1] - x[0][1], x[1][2] - x[0][2]}, dv[3] = {x[3][0] - x[2][0], x[3][1] - x[2][1], x[3][2] - x[2][2]};
+  float duv[3], udv[3], dn[3], vdn[3], dnu[3];
+  barrier_cross(du, v, duv);
+  barrier_cross(u, dv, udv);
+#pragma unroll
+  for (int d = 0; d < 3; ++d) dn[d] = duv[d] + udv[d];
+  barrier_cross(v, dn, vdn);
+  barrier_cross(dn, u, dnu);
+  const float c3 = bb * mp;
+  if constexpr (PSD) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float tu = c3 * (2.f * vdn[d]), tv = c3 * (2.f * dnu[d]);
+      h[0][d] = m * hb[0][d] - tu;
+      h[1][d] = m * hb[1][d] + tu;
+      h[2][d] = m * hb[2][d] - tv;
+      h[3][d] = m * hb[3][d] + tv;
+    }
+  } else {
+    float vn[3], nu[3], dvn[3], ndu[3];
+    barrier_cross(v, n, vn);
+    barrier_cross(n, u, nu);
+    barrier_cross(dv, n, dvn);
+    barrier_cross(n, du, ndu);
+    float dcu[3], dcv[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      dcu[d] = 2.f * vn[d];
+      dcv[d] = 2.f * nu[d];
+    }
+    const float gcx = barrier_dot(dcu, du) + barrier_dot(dcv, dv);
+    const float c1 = mp * bp, c2 = on ? bb * ((-2.f * (gcx / eps)) / eps) : 0.f;  // c2 = b m'' (grad c . x)
+    const float c1c = c1 * gcx, c1g = c1 * gx;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float tu = c1g * dcu[d] + (c2 * dcu[d] + c3 * (2.f * (dvn[d] + vdn[d])));
+      const float tv = c1g * dcv[d] + (c2 * dcv[d] + c3 * (2.f * (dnu[d] + ndu[d])));
+      h[0][d] = (m * hb[0][d] + c1c * ((2.f * w[0]) * r[d])) - tu;
+      h[1][d] = (m * hb[1][d] + c1c * ((2.f * w[1]) * r[d])) + tu;
+      h[2][d] = (m * hb[2][d] + c1c * ((2.f * w[2]) * r[d])) - tv;
+      h[3][d] = (m * hb[3][d] + c1c * ((2.f * w[3]) * r[d])) + tv;
+    }
+  }
+  return barrier_hvp_finish(h);
 }
 
 }  // namespace zsr

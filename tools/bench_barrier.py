@@ -1,4 +1,5 @@
-"""Times the mesh barrier potential (TriMesh.barrier: zs_rocm_mesh_barrier_{incidence,energy,gradient}) next to the same computation written
+"""Times the mesh barrier potential (TriMesh.barrier, TriMesh.barrier_hessian_product: zs_rocm_mesh_barrier_{incidence,energy,gradient,
+hessian_product}) next to the same computation written
 in torch on the GPU -- what a user had before it -- on the two scenes of tools/bench_proximity.py:
 
     surface   the jittered 980 k-triangle surface (--side 700), dHat = half the mean edge
@@ -12,6 +13,9 @@ synchronising, library and torch alternating inside every repetition of the same
     torch_energy       gather the four vertices per pair, the closed forms of include/zensim_rocm/barrier_device.hpp vectorised (every
                        candidate of tri_closest / ee_closest evaluated, the smallest selected), float64 sum
     torch_energy_gradient   the same and index_add_ of the per-pair contributions into the gradient (float atomics: not reproducible)
+    hessian_product    zs_rocm_mesh_barrier_hessian_product, psd = 0: H x for a seeded direction x through the same incidence
+    hessian_product_psd     the same with psd = 1 (the positive semi-definite H+)
+    torch_hessian_product   torch.autograd.functional.hvp over torch_energy (the closed forms differentiated twice on the device)
 Also: the largest differences between the two routes (a sanity check, not a test), pair and incidence counts.
 
     python tools/bench_barrier.py [--side 700] [--sheet 708] [--reps 20] [--warmup 3] [--out profiles/mesh_barrier.json]
@@ -168,8 +172,29 @@ def run_scene(pol, name, v, t, dhat, reps, warmup):
         g.index_add_(0, i1.reshape(-1), g1.reshape(-1, 3))
         keep["e"], keep["g"] = e0.double().sum() + e1.double().sum(), g
 
+    xdir = torch.from_numpy(np.random.default_rng(5).standard_normal((nv, 3)).astype(np.float32)).cuda()
+    hx = torch.empty(nv, 3, dtype=f32, device="cuda")
+
+    def product(psd):
+        assert L.zs_rocm_mesh_barrier_hessian_product(*head, psd, xdir.data_ptr(), starts.data_ptr(), entries.data_ptr(), scratch.data_ptr(),
+                                                      hx.data_ptr(), status.data_ptr()) == 0
+
+    def hessian_product():
+        product(0)
+        keep["hx"] = hx.clone() if "hx" not in keep else keep["hx"]
+
+    def hessian_product_psd():
+        product(1)
+
+    def torch_total(y):
+        return torch_pt(y, tris, ptl, dhat2, False)[0].sum() + torch_ee(y, edges, eel, rest, dhat2, False)[0].sum()
+
+    def torch_hessian_product():
+        keep["thx"] = torch.autograd.functional.hvp(torch_total, x, xdir)[1]
+
     rows = dict(incidence=incidence, energy=energy, torch_energy=torch_energy, energy_gradient=energy_gradient,
-                torch_energy_gradient=torch_energy_gradient)
+                torch_energy_gradient=torch_energy_gradient, hessian_product=hessian_product, torch_hessian_product=torch_hessian_product,
+                hessian_product_psd=hessian_product_psd)
     ms = {k: [] for k in rows}
     stream = torch.cuda.ExternalStream(pol.getStream()) if pol.getStream() else torch.cuda.default_stream()
     pol.sync(False)
@@ -191,7 +216,9 @@ def run_scene(pol, name, v, t, dhat, reps, warmup):
                 incidences=4 * (npt + nee), most_incidences_at_one_vertex=int((starts[1:] - starts[:-1]).max().item()),
                 times={k: stats(x_) for k, x_ in ms.items()},
                 check=dict(energy=float(total.item()), torch_energy=float(keep["e"].item()), largest_gradient=scale,
-                           largest_gradient_difference=float((grad - keep["g"]).abs().max().item()), zero_distance=status.tolist()))
+                           largest_gradient_difference=float((grad - keep["g"]).abs().max().item()),
+                           largest_product=float(keep["hx"].abs().max().item()),
+                           largest_product_difference=float((keep["hx"] - keep["thx"]).abs().max().item()), zero_distance=status.tolist()))
 
 
 def main():

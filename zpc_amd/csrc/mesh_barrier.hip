@@ -10,6 +10,8 @@
 //   incidence built once per pair of lists, independent of the positions: the 4 (npt + nee) (vertex, 4 pair + corner) entries -- EE pairs
 //             numbered behind the PT pairs -- stably sorted by vertex with radix_sort_pair_u32, so a vertex's run is in list order; run
 //             starts = exclusive scan of the per-vertex counts (integer atomics).
+//   product   the Hessian-vector product H x of the same potential, matrix-free: the pair kernels' siblings write (H_pair x) on a pair's four
+//             corners to the same scratch records, and the gather below sums them.  PSD: the positive semi-definite H+ of the header.
 //   gradient  lane = vertex: sums the scratch contributions of its run front to back.  The order is the list's, so two calls give the
 //             same bytes.  A long run (a hub vertex) costs its lane that many loads and nothing else: runs may straddle anything.
 // Built with -ffp-contract=off (zpc_amd/build.py), as every translation unit behind tri_closest / ee_closest.
@@ -161,6 +163,67 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_gather_kernel(const int *__
   grad[3 * (size_t)v + 2] = s2;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- Hessian-vector product
+// lane = pair, as the pair kernels above with the four rows of the direction gathered next to the four vertices: writes (H_pair x) on the
+// pair's corners to the same scratch records, which barrier_gather_kernel then sums per vertex in list order
+template <bool PSD>
+__global__ __launch_bounds__(BAR_BLOCK) void barrier_pt_hvp_kernel(const float *__restrict__ verts, const int *__restrict__ tris, int nv, int nt,
+                                                                   const int *__restrict__ pairs, int npt, float dHat2, float kappa,
+                                                                   const float *__restrict__ dir, float *__restrict__ contrib, int *status) {
+  const int i = blockIdx.x * BAR_BLOCK + threadIdx.x;
+  if (i >= npt) return;
+  const int vi = pairs[2 * (size_t)i], ti = pairs[2 * (size_t)i + 1];
+  float h[4][3] = {};
+  if ((unsigned)vi < (unsigned)nv && (unsigned)ti < (unsigned)nt) {
+    const int i0 = tris[3 * (size_t)ti], i1 = tris[3 * (size_t)ti + 1], i2 = tris[3 * (size_t)ti + 2];
+    if ((unsigned)i0 < (unsigned)nv && (unsigned)i1 < (unsigned)nv && (unsigned)i2 < (unsigned)nv) {
+      float p[3], a[3], b[3], c[3], x[4][3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        p[d] = verts[3 * (size_t)vi + d];
+        a[d] = verts[3 * (size_t)i0 + d];
+        b[d] = verts[3 * (size_t)i1 + d];
+        c[d] = verts[3 * (size_t)i2 + d];
+        x[0][d] = dir[3 * (size_t)vi + d];
+        x[1][d] = dir[3 * (size_t)i0 + d];
+        x[2][d] = dir[3 * (size_t)i1 + d];
+        x[3][d] = dir[3 * (size_t)i2 + d];
+      }
+      if (barrier_pt_hvp<PSD>(p, a, b, c, x, dHat2, kappa, h) == BARRIER_ZERO) atomicAdd(status, 1);
+    }
+  }
+  barrier_store(contrib, (size_t)i, h);
+}
+
+template <bool PSD>
+__global__ __launch_bounds__(BAR_BLOCK) void barrier_ee_hvp_kernel(const float *__restrict__ verts, const int *__restrict__ edges, int nv, int ne,
+                                                                   const float *__restrict__ rest, const int *__restrict__ pairs, int nee, float dHat2,
+                                                                   float kappa, const float *__restrict__ dir, float *__restrict__ contrib,
+                                                                   int *status) {
+  const int i = blockIdx.x * BAR_BLOCK + threadIdx.x;
+  if (i >= nee) return;
+  const int ei = pairs[2 * (size_t)i], ej = pairs[2 * (size_t)i + 1];
+  float h[4][3] = {};
+  if ((unsigned)ei < (unsigned)ne && (unsigned)ej < (unsigned)ne) {
+    const int i0 = edges[2 * (size_t)ei], i1 = edges[2 * (size_t)ei + 1], j0 = edges[2 * (size_t)ej], j1 = edges[2 * (size_t)ej + 1];
+    float a0[3], a1[3], b0[3], b1[3], x[4][3];  // (the mesh's own edge list: its indices are inside the mesh)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      a0[d] = verts[3 * (size_t)i0 + d];
+      a1[d] = verts[3 * (size_t)i1 + d];
+      b0[d] = verts[3 * (size_t)j0 + d];
+      b1[d] = verts[3 * (size_t)j1 + d];
+      x[0][d] = dir[3 * (size_t)i0 + d];
+      x[1][d] = dir[3 * (size_t)i1 + d];
+      x[2][d] = dir[3 * (size_t)j0 + d];
+      x[3][d] = dir[3 * (size_t)j1 + d];
+    }
+    const float eps = rest ? barrier_ee_eps(rest[ei], rest[ej]) : 0.f;
+    if (barrier_ee_hvp<PSD>(a0, a1, b0, b1, x, dHat2, kappa, eps, h) == BARRIER_ZERO) atomicAdd(status + 1, 1);
+  }
+  barrier_store(contrib, (size_t)i, h);
+}
+
 static bool barrier_counts_ok(size_t npt, size_t nee) { return npt + nee < ((size_t)1 << 28); }  // 4 (npt + nee) entries: ints, and one radix sort call
 
 }  // namespace zsr
@@ -278,6 +341,42 @@ int zs_rocm_mesh_barrier_gradient(zs_rocm_policy *pol, const zs_rocm_mesh *m, co
   if (!grad && m && m->nv) return -1;
   return barrier_run(pol, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, starts, entries, scratch, ptEnergy, eeEnergy, total, grad,
                      status);
+}
+
+int zs_rocm_mesh_barrier_hessian_product(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt,
+                                         const int *eePairs, size_t nee, float dHat, float kappa, int mollify, int psd, const float *x,
+                                         const int *starts, const int *entries, float *scratch, float *hx, int *status) {
+  if (!pol || !m || !m->stats || !(dHat > 0.f && dHat <= FLT_MAX) || !(kappa > 0.f && kappa <= FLT_MAX) || (mollify && !m->hasRest)) return -1;
+  if (!barrier_counts_ok(npt, nee) || (npt && !ptPairs) || (nee && !eePairs)) return -1;
+  if (m->nv && (!x || !hx || !starts || (npt + nee && (!entries || !scratch)))) return -1;
+  Launch L(pol, "mesh_barrier_hessian_product");
+  const float *pos = verts ? verts : m->verts;
+  const float dHat2 = dHat * dHat;
+  int *st = status ? status : (int *)L.temp(sizeof(int) * 2);
+  ZSR_CHECK(hipMemsetAsync(st, 0, sizeof(int) * 2, L.stream));
+  if (npt) {
+    const dim3 grid(ceil_div(npt, BAR_BLOCK)), block(BAR_BLOCK);
+    if (psd)
+      hipLaunchKernelGGL((barrier_pt_hvp_kernel<true>), grid, block, 0, L.stream, pos, m->tris, (int)m->nv, (int)m->nt, ptPairs, (int)npt, dHat2,
+                         kappa, x, scratch, st);
+    else
+      hipLaunchKernelGGL((barrier_pt_hvp_kernel<false>), grid, block, 0, L.stream, pos, m->tris, (int)m->nv, (int)m->nt, ptPairs, (int)npt, dHat2,
+                         kappa, x, scratch, st);
+  }
+  if (nee) {
+    const dim3 grid(ceil_div(nee, BAR_BLOCK)), block(BAR_BLOCK);
+    const float *rest = mollify ? m->restLen2 : nullptr;
+    if (psd)
+      hipLaunchKernelGGL((barrier_ee_hvp_kernel<true>), grid, block, 0, L.stream, pos, m->edges, (int)m->nv, (int)m->ne, rest, eePairs, (int)nee,
+                         dHat2, kappa, x, scratch + 12 * npt, st);
+    else
+      hipLaunchKernelGGL((barrier_ee_hvp_kernel<false>), grid, block, 0, L.stream, pos, m->edges, (int)m->nv, (int)m->ne, rest, eePairs, (int)nee,
+                         dHat2, kappa, x, scratch + 12 * npt, st);
+  }
+  if (m->nv)
+    hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
+                       hx);
+  return 0;
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 """Triangle meshes as colliders: TriMesh owns a device mesh object of the library (LBvh over the triangle boxes, face normals, vertex and
 edge pseudonormals) and answers closest-point and signed-distance queries and the proximity pairs of the mesh with itself (vertex-triangle and edge-edge within a
-contact distance) and the IPC barrier potential with its gradient on those pairs; SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
+contact distance) and the IPC barrier potential with its gradient and Hessian-vector product on those pairs; SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
 into a sparse level set.  Set-up code: torch for the plumbing; every query runs in the library's HIP kernels."""
 import ctypes as C
 
@@ -60,6 +60,13 @@ class Barrier:
     (None for a side the Proximity does not have), grad [nv, 3] or None, zero_distance = (PT, EE) pairs at zero distance (their energy is
     +inf and they add nothing to the gradient)"""
     __slots__ = ("energy", "pt_energy", "ee_energy", "grad", "zero_distance")
+
+
+class BarrierHessianProduct:
+    """result of TriMesh.barrier_hessian_product: hx [nv, 3] float32 = H x, pair_terms [npt + nee, 4, 3] float32 (the contributions
+    (H_pair x) on each pair's four corners, PT pairs first: the scratch of the call), zero_distance = (PT, EE) pairs that contribute
+    nothing because their distance is zero"""
+    __slots__ = ("hx", "pair_terms", "zero_distance")
 
 
 class TriMesh:
@@ -253,6 +260,44 @@ class TriMesh:
             rc = lib().zs_rocm_mesh_barrier_energy(*head, *tail, status.data_ptr())
         if rc != 0:
             raise RuntimeError("the barrier call failed")
+        self.pol.syncCtx()
+        z = status.tolist()
+        r.zero_distance = (int(z[0]), int(z[1]))
+        return r
+
+    def barrier_hessian_product(self, prox, dhat, kappa, x, verts=None, mollify=True, psd=False):
+        """H x for a direction x [nv, 3], H the second derivative of the potential of TriMesh.barrier over the pairs of prox, matrix-free:
+        a BarrierHessianProduct.  verts and mollify as for barrier.  psd: the positive semi-definite H+ (every indefinite term discarded
+        analytically; a majorant of H without the mollifier, not the eigenvalue projection of the per-pair blocks), the operator a
+        conjugate-gradient solve can use.  Two calls give the same bytes."""
+        import torch
+        dhat, kappa = float(dhat), float(kappa)
+        for name, val in (("dhat", dhat), ("kappa", kappa)):
+            if not (np.isfinite(val) and val > 0 and np.float32(val) > 0 and np.isfinite(np.float32(val))):
+                raise ValueError("TriMesh.barrier_hessian_product: %s must be finite and positive" % name)
+        if mollify and not getattr(self, "has_rest", False):
+            raise ValueError("TriMesh.barrier_hessian_product: mollify=True needs the rest lengths, call set_rest first")
+        if not isinstance(prox, Proximity):
+            raise ValueError("TriMesh.barrier_hessian_product: prox is the result of TriMesh.proximity")
+        v = None if verts is None else _dev_f32(verts, 3)
+        if v is not None and v.shape[0] != self.nv:
+            raise ValueError("TriMesh.barrier_hessian_product: verts are [nv, 3] positions on the same topology")
+        d = _dev_f32(x, 3)
+        if d.shape[0] != self.nv:
+            raise ValueError("TriMesh.barrier_hessian_product: x is an [nv, 3] direction")
+        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
+        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
+        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+        starts, entries, nscratch = self._incidence(prox, pt, ee)
+        r = BarrierHessianProduct()
+        r.pair_terms = torch.empty(nscratch // 12, 4, 3, dtype=torch.float32, device="cuda")
+        r.hx = torch.empty(self.nv, 3, dtype=torch.float32, device="cuda")
+        status = torch.empty(2, dtype=torch.int32, device="cuda")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        if lib().zs_rocm_mesh_barrier_hessian_product(self.pol.handle, self._h, ptr(v), ptr(pt), npt, ptr(ee), nee, dhat, kappa, 1 if mollify else 0,
+                                                      1 if psd else 0, d.data_ptr(), starts.data_ptr(), entries.data_ptr(),
+                                                      r.pair_terms.data_ptr(), r.hx.data_ptr(), status.data_ptr()) != 0:
+            raise RuntimeError("the barrier Hessian product call failed")
         self.pol.syncCtx()
         z = status.tolist()
         r.zero_distance = (int(z[0]), int(z[1]))
