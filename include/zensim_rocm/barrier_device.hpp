@@ -14,7 +14,7 @@
 //              EE: w = (1 - s, s, -(1 - t), -t), P and Q the closest points on edge i and edge j.
 //              With the parameters of a vertex / an edge / the face substituted this is g_PP / g_PE / g_PT / g_EE wherever those are
 //              defined; where two features tie the distance has no gradient and this is one of its one-sided limits.  No case split.
-//   mollifier  EE only.  u, v the edge vectors, n = u x v, c = |n|^2, eps = 1e-2 restLen2_i restLen2_j:
+//   mollifier  EE only (barrier_ee_frame / _mollifier).  u, v the edge vectors, n = u x v, c = |n|^2, eps = 1e-2 restLen2_i restLen2_j:
 //              m(c) = (2 - c / eps)(c / eps) for c < eps, else 1;  m'(c) = (2 / eps)(1 - c / eps) for c < eps, else 0;
 //              dc/du = 2 (v x n), dc/dv = 2 (n x u), so grad c = (-dc/du, +dc/du, -dc/dv, +dc/dv) on (a0, a1, b0, b1).
 //              energy = m b, gradient = m' b grad c + m b' grad d2.  Exactly parallel edges: c = 0, n = 0, m = 0: exactly zero.
@@ -81,6 +81,42 @@ __host__ __device__ __forceinline__ int barrier_eval(float d2, float dHat2, floa
 // the mollifier threshold of an edge pair from the squared rest lengths
 __host__ __device__ __forceinline__ float barrier_ee_eps(float restLen2I, float restLen2J) { return (1e-2f * restLen2I) * restLen2J; }
 
+__host__ __device__ __forceinline__ float barrier_dot(const float (&a)[3], const float (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+__host__ __device__ __forceinline__ void barrier_cross(const float (&a)[3], const float (&b)[3], float (&c)[3]) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+__host__ __device__ __forceinline__ void barrier_zero(float (&g)[4][3]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g[k][0] = g[k][1] = g[k][2] = 0.f;
+}
+
+// what the gradient and the product of an edge pair share, so that both see the same bits, in two steps (the product runs
+// barrier_hvp_core between them, which keeps its registers down): the edge vectors u, v, the weights w and r = P - Q ...
+struct BarrierEEFrame {
+  float u[3], v[3], w[4], r[3], n[3], c, m = 1.f, mp = 0.f;  // m, m' where c is not below the threshold eps (on)
+  bool on;
+};
+__host__ __device__ __forceinline__ BarrierEEFrame barrier_ee_frame(const EdgeClosest &cl, const float (&a0)[3], const float (&a1)[3],
+                                                                    const float (&b0)[3], const float (&b1)[3]) {
+  BarrierEEFrame f = {{a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]}, {b1[0] - b0[0], b1[1] - b0[1], b1[2] - b0[2]},
+                      {1.f - cl.s, cl.s, -(1.f - cl.t), -cl.t}};
+#pragma unroll
+  for (int d = 0; d < 3; ++d) f.r[d] = (a0[d] + cl.s * f.u[d]) - (b0[d] + cl.t * f.v[d]);
+  return f;
+}
+// ... and n = u x v, c = |n|^2 and the mollifier m(c), m'(c)
+__host__ __device__ __forceinline__ void barrier_ee_mollifier(BarrierEEFrame &f, float eps) {
+  barrier_cross(f.u, f.v, f.n);
+  f.c = barrier_dot(f.n, f.n);
+  f.on = eps >= FLT_MIN && f.c < eps;
+  if (!f.on) return;
+  const float x = f.c / eps;
+  f.m = (2.f - x) * x;
+  f.mp = (2.f / eps) * (1.f - x);
+}
+
 // energy and (GRAD) gradient g[k] on (p, a, b, c) of a point-triangle pair; returns BARRIER_*
 template <bool GRAD>
 __host__ __device__ __forceinline__ int barrier_pt(const float (&p)[3], const float (&a)[3], const float (&b)[3], const float (&c)[3], float dHat2,
@@ -108,34 +144,23 @@ __host__ __device__ __forceinline__ int barrier_ee(const float (&a0)[3], const f
   float bb, bp;
   const int status = barrier_eval(r.dist2, dHat2, kappa, bb, bp);
   energy = bb;
-  if constexpr (GRAD) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) g[k][0] = g[k][1] = g[k][2] = 0.f;
-  }
+  if constexpr (GRAD) barrier_zero(g);
   if (status != BARRIER_ACTIVE) return status;
-  const float u[3] = {a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]}, v[3] = {b1[0] - b0[0], b1[1] - b0[1], b1[2] - b0[2]};
-  const float n[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-  const float c = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
-  float m = 1.f, mp = 0.f;
-  if (eps >= FLT_MIN && c < eps) {
-    const float x = c / eps;
-    m = (2.f - x) * x;
-    mp = (2.f / eps) * (1.f - x);
-  }
-  energy = m * bb;
+  BarrierEEFrame f = barrier_ee_frame(r, a0, a1, b0, b1);
+  barrier_ee_mollifier(f, eps);
+  energy = f.m * bb;
   if constexpr (GRAD) {
-    const float w[4] = {1.f - r.s, r.s, -(1.f - r.t), -r.t};
-    const float A = m * (2.f * bp), B = mp * bb;
-    const float vn[3] = {v[1] * n[2] - v[2] * n[1], v[2] * n[0] - v[0] * n[2], v[0] * n[1] - v[1] * n[0]};
-    const float nu[3] = {n[1] * u[2] - n[2] * u[1], n[2] * u[0] - n[0] * u[2], n[0] * u[1] - n[1] * u[0]};
+    const float A = f.m * (2.f * bp), B = f.mp * bb;
+    float vn[3], nu[3];
+    barrier_cross(f.v, f.n, vn);
+    barrier_cross(f.n, f.u, nu);
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-      const float diff = (a0[d] + r.s * u[d]) - (b0[d] + r.t * v[d]);
       const float dcu = 2.f * vn[d], dcv = 2.f * nu[d];
-      g[0][d] = B * -dcu + (A * w[0]) * diff;
-      g[1][d] = B * dcu + (A * w[1]) * diff;
-      g[2][d] = B * -dcv + (A * w[2]) * diff;
-      g[3][d] = B * dcv + (A * w[3]) * diff;
+      g[0][d] = B * -dcu + (A * f.w[0]) * f.r[d];
+      g[1][d] = B * dcu + (A * f.w[1]) * f.r[d];
+      g[2][d] = B * -dcv + (A * f.w[2]) * f.r[d];
+      g[3][d] = B * dcv + (A * f.w[3]) * f.r[d];
     }
   }
   return status;
@@ -155,13 +180,6 @@ __host__ __device__ __forceinline__ int barrier_eval2(float d2, float dHat2, flo
   }
   bpp = dd;
   return status;
-}
-
-__host__ __device__ __forceinline__ float barrier_dot(const float (&a)[3], const float (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-__host__ __device__ __forceinline__ void barrier_cross(const float (&a)[3], const float (&b)[3], float (&c)[3]) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 // H_b x (PSD: H+_b x) on the four corners from the weights w, r = P - Q and up to two free parameters: f1 / f2 say whether slot 1 / 2 is
@@ -213,10 +231,8 @@ __host__ __device__ __forceinline__ int barrier_hvp_finish(float (&h)[4][3]) {
   for (int k = 0; k < 4; ++k)
 #pragma unroll
     for (int d = 0; d < 3; ++d) ok = ok && fabsf(h[k][d]) <= FLT_MAX;
-  if (ok) return BARRIER_ACTIVE;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) h[k][0] = h[k][1] = h[k][2] = 0.f;
-  return BARRIER_ZERO;
+  if (!ok) barrier_zero(h);
+  return ok ? BARRIER_ACTIVE : BARRIER_ZERO;
 }
 
 // h[k] = (H x)_k on (p, a, b, c) of a point-triangle pair for the direction x[k] at those vertices; PSD: the H+ of the header; returns BARRIER_*
@@ -226,8 +242,7 @@ __host__ __device__ __forceinline__ int barrier_pt_hvp(const float (&p)[3], cons
   const TriClosest cl = tri_closest(p, a, b, c);
   float bb, bp, bpp;
   const int status = barrier_eval2(cl.dist2, dHat2, kappa, bb, bp, bpp);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) h[k][0] = h[k][1] = h[k][2] = 0.f;
+  barrier_zero(h);
   if (status != BARRIER_ACTIVE) return status;
   const int ft = cl.feature;
   const bool face = ft == TRI_FACE, eab = ft == TRI_EDGE_AB, ebc = ft == TRI_EDGE_BC, eca = ft == TRI_EDGE_CA;
@@ -253,73 +268,56 @@ __host__ __device__ __forceinline__ int barrier_ee_hvp(const float (&a0)[3], con
   const EdgeClosest cl = ee_closest(a0, a1, b0, b1);
   float bb, bp, bpp;
   const int status = barrier_eval2(cl.dist2, dHat2, kappa, bb, bp, bpp);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) h[k][0] = h[k][1] = h[k][2] = 0.f;
+  barrier_zero(h);
   if (status != BARRIER_ACTIVE) return status;
   const bool fs = cl.category / 3 == EE_INTERIOR, ft = cl.category % 3 == EE_INTERIOR;
-  const float u[3] = {a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]}, v[3] = {b1[0] - b0[0], b1[1] - b0[1], b1[2] - b0[2]};
+  BarrierEEFrame f = barrier_ee_frame(cl, a0, a1, b0, b1);
   const float d1[4] = {fs ? -1.f : 0.f, fs ? 1.f : 0.f, 0.f, 0.f}, d2[4] = {0.f, 0.f, ft ? 1.f : 0.f, ft ? -1.f : 0.f};
-  const float w[4] = {1.f - cl.s, cl.s, -(1.f - cl.t), -cl.t};
-  float r[3], r1[3], r2[3];
+  float r1[3], r2[3];
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
-    r[d] = (a0[d] + cl.s * u[d]) - (b0[d] + cl.t * v[d]);
-    r1[d] = fs ? u[d] : 0.f;
+    r1[d] = fs ? f.u[d] : 0.f;
     r2[d] = ft ? b0[d] - b1[d] : 0.f;
   }
   float hb[4][3];
-  const float gx = barrier_hvp_core<PSD>(w, r, fs, ft, d1, d2, r1, r2, x, bp, bpp, hb);
-  float n[3];
-  barrier_cross(u, v, n);
-  const float c = barrier_dot(n, n);
-  float m = 1.f, mp = 0.f;
-  const bool on = eps >= FLT_MIN && c < eps;
-  if (on) {
-    const float xx = c / eps;
-    m = (2.f - xx) * xx;
-    mp = (2.f / eps) * (1.f - xx);
-  }
+  const float gx = barrier_hvp_core<PSD>(f.w, f.r, fs, ft, d1, d2, r1, r2, x, bp, bpp, hb);
+  barrier_ee_mollifier(f, eps);
   const float du[3] = {x[1][0] - x[0][0], x[1][1] - x[0][1], x[1][2] - x[0][2]}, dv[3] = {x[3][0] - x[2][0], x[3][1] - x[2][1], x[3][2] - x[2][2]};
   float duv[3], udv[3], dn[3], vdn[3], dnu[3];
-  barrier_cross(du, v, duv);
-  barrier_cross(u, dv, udv);
+  barrier_cross(du, f.v, duv);
+  barrier_cross(f.u, dv, udv);
 #pragma unroll
   for (int d = 0; d < 3; ++d) dn[d] = duv[d] + udv[d];
-  barrier_cross(v, dn, vdn);
-  barrier_cross(dn, u, dnu);
-  const float c3 = bb * mp;
+  barrier_cross(f.v, dn, vdn);
+  barrier_cross(dn, f.u, dnu);
+  const float c3 = bb * f.mp;
   if constexpr (PSD) {
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       const float tu = c3 * (2.f * vdn[d]), tv = c3 * (2.f * dnu[d]);
-      h[0][d] = m * hb[0][d] - tu;
-      h[1][d] = m * hb[1][d] + tu;
-      h[2][d] = m * hb[2][d] - tv;
-      h[3][d] = m * hb[3][d] + tv;
+      h[0][d] = f.m * hb[0][d] - tu;
+      h[1][d] = f.m * hb[1][d] + tu;
+      h[2][d] = f.m * hb[2][d] - tv;
+      h[3][d] = f.m * hb[3][d] + tv;
     }
   } else {
     float vn[3], nu[3], dvn[3], ndu[3];
-    barrier_cross(v, n, vn);
-    barrier_cross(n, u, nu);
-    barrier_cross(dv, n, dvn);
-    barrier_cross(n, du, ndu);
-    float dcu[3], dcv[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      dcu[d] = 2.f * vn[d];
-      dcv[d] = 2.f * nu[d];
-    }
+    barrier_cross(f.v, f.n, vn);
+    barrier_cross(f.n, f.u, nu);
+    barrier_cross(dv, f.n, dvn);
+    barrier_cross(f.n, du, ndu);
+    const float dcu[3] = {2.f * vn[0], 2.f * vn[1], 2.f * vn[2]}, dcv[3] = {2.f * nu[0], 2.f * nu[1], 2.f * nu[2]};
     const float gcx = barrier_dot(dcu, du) + barrier_dot(dcv, dv);
-    const float c1 = mp * bp, c2 = on ? bb * ((-2.f * (gcx / eps)) / eps) : 0.f;  // c2 = b m'' (grad c . x)
+    const float c1 = f.mp * bp, c2 = f.on ? bb * ((-2.f * (gcx / eps)) / eps) : 0.f;  // c2 = b m'' (grad c . x)
     const float c1c = c1 * gcx, c1g = c1 * gx;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       const float tu = c1g * dcu[d] + (c2 * dcu[d] + c3 * (2.f * (dvn[d] + vdn[d])));
       const float tv = c1g * dcv[d] + (c2 * dcv[d] + c3 * (2.f * (dnu[d] + ndu[d])));
-      h[0][d] = (m * hb[0][d] + c1c * ((2.f * w[0]) * r[d])) - tu;
-      h[1][d] = (m * hb[1][d] + c1c * ((2.f * w[1]) * r[d])) + tu;
-      h[2][d] = (m * hb[2][d] + c1c * ((2.f * w[2]) * r[d])) - tv;
-      h[3][d] = (m * hb[3][d] + c1c * ((2.f * w[3]) * r[d])) + tv;
+      h[0][d] = (f.m * hb[0][d] + c1c * ((2.f * f.w[0]) * f.r[d])) - tu;
+      h[1][d] = (f.m * hb[1][d] + c1c * ((2.f * f.w[1]) * f.r[d])) + tu;
+      h[2][d] = (f.m * hb[2][d] + c1c * ((2.f * f.w[2]) * f.r[d])) - tv;
+      h[3][d] = (f.m * hb[3][d] + c1c * ((2.f * f.w[3]) * f.r[d])) + tv;
     }
   }
   return barrier_hvp_finish(h);

@@ -1,9 +1,9 @@
 """Mesh barrier potential on the GPU (zpc_amd/csrc/mesh_barrier.hip, TriMesh.set_rest / TriMesh.barrier) against the float64 reference and
 the derived bounds of tests/ref64_barrier.py: energies per pair, the float64 total and the gradient per vertex on every scene of
 ref64_proximity.SCENES, mollified and not; runs of more than 64 incidences; determinism on `large`; trial positions; a pair at zero
-distance; the invariants; the argument checks.  The constraint sets are the lists TriMesh.proximity returns; the reference evaluates the
-same lists.  No pair and no vertex is left out of a comparison: where a bound is infinite (an interval of distances that reaches zero) the
-line printed says how many.  Prints one `BARRIER <what> ...` line per check.
+distance; the invariants; the argument checks; lists with indices outside the mesh.  The constraint sets are the lists TriMesh.proximity
+returns; the reference evaluates the same lists.  No pair and no vertex is left out of a comparison: where a bound is infinite (an interval
+of distances that reaches zero) the line printed says how many.  Prints one `BARRIER <what> ...` line per check.
 
 Measured on an MI355X: worst vertex gradient 0.012 of its bound mollified (stack) and 0.34 unmollified (torus), worst pair energy 0.044
 (torus, EE); 4 pairs and 16 vertices of `stack` have an infinite bound; most incidences at one vertex 821 (fan); the file runs in 2.7 s."""
@@ -268,3 +268,68 @@ def test_arguments(pol):
     assert abs(both - float(full.energy.item())) <= 1e-14 * both and both > 0
     # unmollified EE energies are at least the mollified ones (m <= 1), PT energies do not depend on the mollifier
     assert _np(plain.pt_energy).tobytes() == _np(full.pt_energy).tobytes() and (_np(plain.ee_energy) >= _np(full.ee_energy)).all()
+
+
+# ------------------------------------------------------------------------------------------------ 7: indices outside the mesh
+def _spliced(pairs, bad):
+    """pairs with the four rows of bad at positions 0, 255, 256 and last (the ends of the first workgroup, the start of the second, the
+    ragged last one); returns the list and the mask of the rows that came from pairs"""
+    n = len(pairs) + 4
+    at = [0, 255, 256, n - 1]
+    keep = np.ones(n, bool)
+    keep[at] = False
+    out = np.empty((n, 2), np.int32)
+    out[at], out[keep] = bad, pairs
+    return out, keep
+
+
+def test_pairs_with_indices_outside_the_mesh_are_inactive(pol):
+    from zpc_amd import lib
+    from zpc_amd.mesh import Proximity
+    import ref64_barrier_hessian as rh
+    mesh, dhat = _mesh(pol, "sheets")
+    nv, nt, ne = mesh.nv, mesh.nt, mesh.num_edges
+    clean = mesh.proximity(dhat)
+    assert len(clean.pt_pairs) > 512 and len(clean.ee_pairs) > 512      # the bad rows fall into three different workgroups per kind
+    pt, kpt = _spliced(_np(clean.pt_pairs), [(-1, 0), (nv, 0), (0, -1), (0, nt)])
+    ee, kee = _spliced(_np(clean.ee_pairs), [(-1, 0), (ne, 0), (0, -1), (0, ne)])
+    keep = np.concatenate([kpt, kee])
+    dirty = Proximity()
+    dirty.pt_pairs, dirty.ee_pairs = torch.from_numpy(pt).cuda(), torch.from_numpy(ee).cuda()
+
+    def same(what, zero, rows, out):
+        """zero_distance, the per-pair rows (PT then EE) and the per-vertex or total output, each as (clean, dirty)"""
+        assert zero[1] == zero[0], what
+        c, d = (r.reshape(len(r), -1).view(np.uint32) for r in rows)
+        assert len(d) == len(keep) and (d[~keep] == 0).all(), what
+        assert np.array_equal(d[keep], c), what
+        assert out[1].tobytes() == out[0].tobytes(), what
+
+    def records(p):
+        """the [4][3] records of the gradient call, which TriMesh.barrier does not return: the C entry on the incidence kept on p"""
+        starts, entries, nscratch = p._incidence
+        scratch = torch.empty(nscratch, dtype=torch.float32, device="cuda")
+        grad = torch.empty(nv, 3, dtype=torch.float32, device="cuda")
+        assert lib().zs_rocm_mesh_barrier_gradient(pol.handle, mesh.handle, None, p.pt_pairs.data_ptr(), len(p.pt_pairs), p.ee_pairs.data_ptr(),
+                                                   len(p.ee_pairs), dhat, KAPPA, 1, starts.data_ptr(), entries.data_ptr(), scratch.data_ptr(),
+                                                   None, None, None, grad.data_ptr(), None) == 0
+        pol.syncCtx()
+        return _np(scratch).reshape(-1, 4, 3), _np(grad)
+
+    B = [mesh.barrier(p, dhat, KAPPA) for p in (clean, dirty)]
+    energies = [np.concatenate([_np(b.pt_energy), _np(b.ee_energy)]) for b in B]
+    same("energy", [b.zero_distance for b in B], energies, [_np(b.energy) for b in B])
+    assert float(B[0].energy.item()) > 0
+    recs = [records(p) for p in (clean, dirty)]
+    same("gradient", [b.zero_distance for b in B], [r[0] for r in recs], [_np(b.grad) for b in B])
+    assert recs[1][1].tobytes() == _np(B[1].grad).tobytes() and np.abs(_np(B[0].grad)).max() > 0
+    E = mesh.barrier(dirty, dhat, KAPPA, gradient=False)      # the energy-only kernels decide the same
+    assert np.concatenate([_np(E.pt_energy), _np(E.ee_energy)]).tobytes() == energies[1].tobytes()
+    assert _np(E.energy).tobytes() == _np(B[1].energy).tobytes() and E.zero_distance == B[1].zero_distance
+    x = rh.direction(nv, 1)
+    for psd in (False, True):
+        P = [mesh.barrier_hessian_product(p, dhat, KAPPA, x, psd=psd) for p in (clean, dirty)]
+        same("product, psd %s" % psd, [p.zero_distance for p in P], [_np(p.pair_terms) for p in P], [_np(p.hx) for p in P])
+        assert np.abs(_np(P[0].hx)).max() > 0
+    print("BARRIER indices outside the mesh: %d + 4 PT, %d + 4 EE pairs; the 8 bad rows are zero, every other row, the total, grad and hx are "
+          "those of the clean lists" % (len(clean.pt_pairs), len(clean.ee_pairs)))

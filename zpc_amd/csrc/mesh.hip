@@ -32,8 +32,6 @@
 
 namespace zsr {
 
-void exclusive_scan_u32(Launch &L, const unsigned *in, size_t n, unsigned *out);
-void radix_sort_pair_u32(Launch &L, const unsigned *kin, const int *vin, unsigned *kout, int *vout, size_t n, int sbit, int ebit);
 void radix_sort_pair_u64(Launch &L, const unsigned long long *kin, const int *vin, unsigned long long *kout, int *vout, size_t n, int sbit,
                          int ebit);
 

@@ -53,6 +53,10 @@ struct zs_rocm_mesh {
 
 namespace zsr {
 
+// primitives.hip
+void exclusive_scan_u32(Launch &L, const unsigned *in, size_t n, unsigned *out);
+void radix_sort_pair_u32(Launch &L, const unsigned *kin, const int *vin, unsigned *kout, int *vout, size_t n, int sbit, int ebit);
+
 // mesh_proximity.hip: after new vertex positions -- the packed nodes are stale, the edge tree (if built) is refitted; -1 on failure
 int mesh_proximity_refit(zs_rocm_policy *pol, zs_rocm_mesh &m);
 

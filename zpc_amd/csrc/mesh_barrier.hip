@@ -1,19 +1,20 @@
-// mesh_barrier.hip -- the IPC contact potential of a mesh on a proximity constraint set for gfx950: total energy and per-vertex gradient
-// over the PT and EE pair lists of mesh_proximity.hip, at the mesh's own or at trial positions (include/zensim_rocm/barrier_device.hpp
-// has the math).  Bit-reproducible: no float atomics anywhere.
+// mesh_barrier.hip -- the IPC contact potential of a mesh on a proximity constraint set for gfx950: total energy, per-vertex gradient and
+// matrix-free Hessian-vector product over the PT and EE pair lists of mesh_proximity.hip, at the mesh's own or at trial positions
+// (include/zensim_rocm/barrier_device.hpp has the math).  Bit-reproducible: no float atomics anywhere.
 //
-//   pairs     lane = pair.  Gathers the four vertices, recomputes distance, parameters and feature at the given positions, writes the
-//             pair's energy and (GRAD) its [4][3] contributions to a scratch array, once.  Zero-distance pairs are counted with an integer
-//             atomic (a count has no order).  Indices outside the mesh make a pair inactive.
+//   pairs     lane = pair, one kernel template for both kinds and every operation (energy, gradient, the Hessian-vector product H x and its
+//             positive semi-definite H+ x of the header).  barrier_corners resolves the pair's four vertices -- indices outside the mesh make
+//             a pair inactive -- then the kernel gathers them (a product: the four rows of the direction as well), recomputes distance,
+//             parameters and feature at the given positions and writes the pair's energy and / or its [4][3] contributions to a scratch
+//             array, once.  Zero-distance pairs are counted with an integer atomic (a count has no order).  A new per-pair quantity is one
+//             more BARRIER_OP_* and its branch in barrier_pair_kernel.
 //   energy    float64 sum of the per-pair energies, PT then EE, in a fixed order: workgroup g sums elements [g, g + 1) x RED_CHUNK, thread
 //             t the elements t, t + 256, .. of the chunk, then an LDS tree; one workgroup sums the partials the same way.
 //   incidence built once per pair of lists, independent of the positions: the 4 (npt + nee) (vertex, 4 pair + corner) entries -- EE pairs
 //             numbered behind the PT pairs -- stably sorted by vertex with radix_sort_pair_u32, so a vertex's run is in list order; run
 //             starts = exclusive scan of the per-vertex counts (integer atomics).
-//   product   the Hessian-vector product H x of the same potential, matrix-free: the pair kernels' siblings write (H_pair x) on a pair's four
-//             corners to the same scratch records, and the gather below sums them.  PSD: the positive semi-definite H+ of the header.
-//   gradient  lane = vertex: sums the scratch contributions of its run front to back.  The order is the list's, so two calls give the
-//             same bytes.  A long run (a hub vertex) costs its lane that many loads and nothing else: runs may straddle anything.
+//   gather    lane = vertex: sums the scratch contributions (of the gradient or of a product) of its run front to back.  The order is the
+//             list's, so two calls give the same bytes.  A long run (a hub vertex) costs its lane that many loads and nothing else.
 // Built with -ffp-contract=off (zpc_amd/build.py), as every translation unit behind tri_closest / ee_closest.
 #include <cfloat>
 
@@ -21,9 +22,6 @@
 #include "../../include/zensim_rocm/barrier_device.hpp"
 
 namespace zsr {
-
-void exclusive_scan_u32(Launch &L, const unsigned *in, size_t n, unsigned *out);
-void radix_sort_pair_u32(Launch &L, const unsigned *kin, const int *vin, unsigned *kout, int *vout, size_t n, int sbit, int ebit);
 
 constexpr int BAR_BLOCK = 256, RED_CHUNK = 4096;
 
@@ -43,55 +41,74 @@ __device__ __forceinline__ void barrier_store(float *contrib, size_t pair, const
   o[2] = make_float4(g[2][2], g[3][0], g[3][1], g[3][2]);
 }
 
-template <bool GRAD>
-__global__ __launch_bounds__(BAR_BLOCK) void barrier_pt_kernel(const float *__restrict__ verts, const int *__restrict__ tris, int nv, int nt,
-                                                               const int *__restrict__ pairs, int npt, float dHat2, float kappa,
-                                                               float *__restrict__ energy, float *__restrict__ contrib, int *status) {
-  const int i = blockIdx.x * BAR_BLOCK + threadIdx.x;
-  if (i >= npt) return;
-  const int vi = pairs[2 * (size_t)i], ti = pairs[2 * (size_t)i + 1];
-  float e = 0.f, g[4][3] = {};
-  if ((unsigned)vi < (unsigned)nv && (unsigned)ti < (unsigned)nt) {
-    const int i0 = tris[3 * (size_t)ti], i1 = tris[3 * (size_t)ti + 1], i2 = tris[3 * (size_t)ti + 2];
-    if ((unsigned)i0 < (unsigned)nv && (unsigned)i1 < (unsigned)nv && (unsigned)i2 < (unsigned)nv) {
-      float p[3], a[3], b[3], c[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        p[d] = verts[3 * (size_t)vi + d];
-        a[d] = verts[3 * (size_t)i0 + d];
-        b[d] = verts[3 * (size_t)i1 + d];
-        c[d] = verts[3 * (size_t)i2 + d];
-      }
-      if (barrier_pt<GRAD>(p, a, b, c, dHat2, kappa, e, g) == BARRIER_ZERO) atomicAdd(status, 1);
-    }
+enum { BARRIER_OP_ENERGY, BARRIER_OP_GRADIENT, BARRIER_OP_PRODUCT, BARRIER_OP_PRODUCT_PSD };
+
+// one pair list of one kind and what the pair kernel reads and writes for it
+struct BarrierPairs {
+  const float *verts;  // [nv][3] positions
+  const int *prims;    // the kind's primitives: tris [np][3] (PT) or edges [np][2] (EE)
+  int nv, np;
+  const float *rest;  // EE: the squared rest lengths [np]; null: unmollified
+  const int *pairs;   // [n][2]: (vertex, triangle) or (edge, edge)
+  int n;
+  float dHat2, kappa;
+  const float *dir;         // [nv][3], a product only
+  float *energy, *contrib;  // [n] (energy, gradient) and the [n][4][3] records (all but energy)
+  int *status;              // [2] zero-distance counts, PT then EE
+};
+
+// the four corner vertices of pair i and the mollifier threshold (0: none); false: an index outside the mesh, the pair is inactive.  Every
+// load sits behind the check of its index; an edge's own two vertices are not checked (the mesh's own edge list: they are inside the mesh)
+template <bool EE>
+__device__ __forceinline__ bool barrier_corners(const BarrierPairs &a, int i, int (&idx)[4], float &eps) {
+  const int p = a.pairs[2 * (size_t)i], q = a.pairs[2 * (size_t)i + 1];
+  eps = 0.f;
+  if constexpr (EE) {
+    if (!((unsigned)p < (unsigned)a.np && (unsigned)q < (unsigned)a.np)) return false;
+    idx[0] = a.prims[2 * (size_t)p], idx[1] = a.prims[2 * (size_t)p + 1], idx[2] = a.prims[2 * (size_t)q], idx[3] = a.prims[2 * (size_t)q + 1];
+    if (a.rest) eps = barrier_ee_eps(a.rest[p], a.rest[q]);
+    return true;
+  } else {
+    if (!((unsigned)p < (unsigned)a.nv && (unsigned)q < (unsigned)a.np)) return false;
+    idx[0] = p, idx[1] = a.prims[3 * (size_t)q], idx[2] = a.prims[3 * (size_t)q + 1], idx[3] = a.prims[3 * (size_t)q + 2];
+    return (unsigned)idx[1] < (unsigned)a.nv && (unsigned)idx[2] < (unsigned)a.nv && (unsigned)idx[3] < (unsigned)a.nv;
   }
-  energy[i] = e;
-  if constexpr (GRAD) barrier_store(contrib, (size_t)i, g);
 }
 
-template <bool GRAD>
-__global__ __launch_bounds__(BAR_BLOCK) void barrier_ee_kernel(const float *__restrict__ verts, const int *__restrict__ edges, int nv, int ne,
-                                                               const float *__restrict__ rest, const int *__restrict__ pairs, int nee, float dHat2,
-                                                               float kappa, float *__restrict__ energy, float *__restrict__ contrib, int *status) {
-  const int i = blockIdx.x * BAR_BLOCK + threadIdx.x;
-  if (i >= nee) return;
-  const int ei = pairs[2 * (size_t)i], ej = pairs[2 * (size_t)i + 1];
-  float e = 0.f, g[4][3] = {};
-  if ((unsigned)ei < (unsigned)ne && (unsigned)ej < (unsigned)ne) {
-    const int i0 = edges[2 * (size_t)ei], i1 = edges[2 * (size_t)ei + 1], j0 = edges[2 * (size_t)ej], j1 = edges[2 * (size_t)ej + 1];
-    float a0[3], a1[3], b0[3], b1[3];  // (the mesh's own edge list: its indices are inside the mesh)
+__device__ __forceinline__ void barrier_rows(const float *__restrict__ src, const int (&idx)[4], float (&out)[4][3]) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      a0[d] = verts[3 * (size_t)i0 + d];
-      a1[d] = verts[3 * (size_t)i1 + d];
-      b0[d] = verts[3 * (size_t)j0 + d];
-      b1[d] = verts[3 * (size_t)j1 + d];
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) out[k][d] = src[3 * (size_t)idx[k] + d];
+}
+
+template <bool EE, int OP>
+__global__ __launch_bounds__(BAR_BLOCK) void barrier_pair_kernel(const BarrierPairs a) {
+  const int i = blockIdx.x * BAR_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  constexpr bool PRODUCT = OP == BARRIER_OP_PRODUCT || OP == BARRIER_OP_PRODUCT_PSD;
+  int idx[4];
+  float eps, e = 0.f, g[4][3] = {};
+  if (barrier_corners<EE>(a, i, idx, eps)) {
+    float p[4][3];
+    barrier_rows(a.verts, idx, p);
+    int status;
+    if constexpr (PRODUCT) {
+      float x[4][3];
+      barrier_rows(a.dir, idx, x);
+      if constexpr (EE)
+        status = barrier_ee_hvp<OP == BARRIER_OP_PRODUCT_PSD>(p[0], p[1], p[2], p[3], x, a.dHat2, a.kappa, eps, g);
+      else
+        status = barrier_pt_hvp<OP == BARRIER_OP_PRODUCT_PSD>(p[0], p[1], p[2], p[3], x, a.dHat2, a.kappa, g);
+    } else if constexpr (EE) {
+      status = barrier_ee<OP == BARRIER_OP_GRADIENT>(p[0], p[1], p[2], p[3], a.dHat2, a.kappa, eps, e, g);
+    } else {
+      status = barrier_pt<OP == BARRIER_OP_GRADIENT>(p[0], p[1], p[2], p[3], a.dHat2, a.kappa, e, g);
     }
-    const float eps = rest ? barrier_ee_eps(rest[ei], rest[ej]) : 0.f;
-    if (barrier_ee<GRAD>(a0, a1, b0, b1, dHat2, kappa, eps, e, g) == BARRIER_ZERO) atomicAdd(status + 1, 1);
+    if (status == BARRIER_ZERO) atomicAdd(a.status + EE, 1);
   }
-  energy[i] = e;
-  if constexpr (GRAD) barrier_store(contrib, (size_t)i, g);
+  if constexpr (!PRODUCT) a.energy[i] = e;
+  if constexpr (OP != BARRIER_OP_ENERGY) barrier_store(a.contrib, (size_t)i, g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the float64 total
@@ -163,68 +180,45 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_gather_kernel(const int *__
   grad[3 * (size_t)v + 2] = s2;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- Hessian-vector product
-// lane = pair, as the pair kernels above with the four rows of the direction gathered next to the four vertices: writes (H_pair x) on the
-// pair's corners to the same scratch records, which barrier_gather_kernel then sums per vertex in list order
-template <bool PSD>
-__global__ __launch_bounds__(BAR_BLOCK) void barrier_pt_hvp_kernel(const float *__restrict__ verts, const int *__restrict__ tris, int nv, int nt,
-                                                                   const int *__restrict__ pairs, int npt, float dHat2, float kappa,
-                                                                   const float *__restrict__ dir, float *__restrict__ contrib, int *status) {
-  const int i = blockIdx.x * BAR_BLOCK + threadIdx.x;
-  if (i >= npt) return;
-  const int vi = pairs[2 * (size_t)i], ti = pairs[2 * (size_t)i + 1];
-  float h[4][3] = {};
-  if ((unsigned)vi < (unsigned)nv && (unsigned)ti < (unsigned)nt) {
-    const int i0 = tris[3 * (size_t)ti], i1 = tris[3 * (size_t)ti + 1], i2 = tris[3 * (size_t)ti + 2];
-    if ((unsigned)i0 < (unsigned)nv && (unsigned)i1 < (unsigned)nv && (unsigned)i2 < (unsigned)nv) {
-      float p[3], a[3], b[3], c[3], x[4][3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        p[d] = verts[3 * (size_t)vi + d];
-        a[d] = verts[3 * (size_t)i0 + d];
-        b[d] = verts[3 * (size_t)i1 + d];
-        c[d] = verts[3 * (size_t)i2 + d];
-        x[0][d] = dir[3 * (size_t)vi + d];
-        x[1][d] = dir[3 * (size_t)i0 + d];
-        x[2][d] = dir[3 * (size_t)i1 + d];
-        x[3][d] = dir[3 * (size_t)i2 + d];
-      }
-      if (barrier_pt_hvp<PSD>(p, a, b, c, x, dHat2, kappa, h) == BARRIER_ZERO) atomicAdd(status, 1);
-    }
-  }
-  barrier_store(contrib, (size_t)i, h);
-}
-
-template <bool PSD>
-__global__ __launch_bounds__(BAR_BLOCK) void barrier_ee_hvp_kernel(const float *__restrict__ verts, const int *__restrict__ edges, int nv, int ne,
-                                                                   const float *__restrict__ rest, const int *__restrict__ pairs, int nee, float dHat2,
-                                                                   float kappa, const float *__restrict__ dir, float *__restrict__ contrib,
-                                                                   int *status) {
-  const int i = blockIdx.x * BAR_BLOCK + threadIdx.x;
-  if (i >= nee) return;
-  const int ei = pairs[2 * (size_t)i], ej = pairs[2 * (size_t)i + 1];
-  float h[4][3] = {};
-  if ((unsigned)ei < (unsigned)ne && (unsigned)ej < (unsigned)ne) {
-    const int i0 = edges[2 * (size_t)ei], i1 = edges[2 * (size_t)ei + 1], j0 = edges[2 * (size_t)ej], j1 = edges[2 * (size_t)ej + 1];
-    float a0[3], a1[3], b0[3], b1[3], x[4][3];  // (the mesh's own edge list: its indices are inside the mesh)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      a0[d] = verts[3 * (size_t)i0 + d];
-      a1[d] = verts[3 * (size_t)i1 + d];
-      b0[d] = verts[3 * (size_t)j0 + d];
-      b1[d] = verts[3 * (size_t)j1 + d];
-      x[0][d] = dir[3 * (size_t)i0 + d];
-      x[1][d] = dir[3 * (size_t)i1 + d];
-      x[2][d] = dir[3 * (size_t)j0 + d];
-      x[3][d] = dir[3 * (size_t)j1 + d];
-    }
-    const float eps = rest ? barrier_ee_eps(rest[ei], rest[ej]) : 0.f;
-    if (barrier_ee_hvp<PSD>(a0, a1, b0, b1, x, dHat2, kappa, eps, h) == BARRIER_ZERO) atomicAdd(status + 1, 1);
-  }
-  barrier_store(contrib, (size_t)i, h);
-}
-
 static bool barrier_counts_ok(size_t npt, size_t nee) { return npt + nee < ((size_t)1 << 28); }  // 4 (npt + nee) entries: ints, and one radix sort call
+
+// the checks the energy, the gradient and the product have in common
+static bool barrier_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const int *ptPairs, size_t npt, const int *eePairs, size_t nee,
+                            float dHat, float kappa, int mollify) {
+  if (!pol || !m || !m->stats || !(dHat > 0.f && dHat <= FLT_MAX) || !(kappa > 0.f && kappa <= FLT_MAX) || (mollify && !m->hasRest)) return false;
+  return barrier_counts_ok(npt, nee) && !(npt && !ptPairs) && !(nee && !eePairs);
+}
+
+// the caller's two zero-distance counts or a temporary, zeroed
+static int *barrier_status(Launch &L, int *status) {
+  int *st = status ? status : (int *)L.temp(sizeof(int) * 2);
+  ZSR_CHECK(hipMemsetAsync(st, 0, sizeof(int) * 2, L.stream));
+  return st;
+}
+
+template <int OP>
+static void barrier_launch_op(Launch &L, const BarrierPairs &pt, const BarrierPairs &ee) {
+  const dim3 block(BAR_BLOCK);
+  if (pt.n) hipLaunchKernelGGL((barrier_pair_kernel<false, OP>), dim3(ceil_div(pt.n, BAR_BLOCK)), block, 0, L.stream, pt);
+  if (ee.n) hipLaunchKernelGGL((barrier_pair_kernel<true, OP>), dim3(ceil_div(ee.n, BAR_BLOCK)), block, 0, L.stream, ee);
+}
+
+// the pair kernels of one operation: the PT list, then the EE list, whose records follow the PT list's
+static void barrier_launch_pairs(Launch &L, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
+                                 size_t nee, float dHat, float kappa, int mollify, int op, const float *dir, float *ptEnergy, float *eeEnergy,
+                                 float *scratch, int *status) {
+  const BarrierPairs pt = {verts ? verts : m->verts, m->tris, (int)m->nv, (int)m->nt, nullptr, ptPairs, (int)npt, dHat * dHat, kappa, dir,
+                           ptEnergy, scratch, barrier_status(L, status)};
+  BarrierPairs ee = pt;
+  ee.prims = m->edges, ee.np = (int)m->ne, ee.rest = mollify ? m->restLen2 : nullptr;
+  ee.pairs = eePairs, ee.n = (int)nee, ee.energy = eeEnergy, ee.contrib = scratch ? scratch + 12 * npt : nullptr;
+  switch (op) {
+    case BARRIER_OP_ENERGY: return barrier_launch_op<BARRIER_OP_ENERGY>(L, pt, ee);
+    case BARRIER_OP_GRADIENT: return barrier_launch_op<BARRIER_OP_GRADIENT>(L, pt, ee);
+    case BARRIER_OP_PRODUCT: return barrier_launch_op<BARRIER_OP_PRODUCT>(L, pt, ee);
+    default: return barrier_launch_op<BARRIER_OP_PRODUCT_PSD>(L, pt, ee);
+  }
+}
 
 }  // namespace zsr
 
@@ -286,36 +280,13 @@ int zs_rocm_mesh_barrier_incidence(zs_rocm_policy *pol, const zs_rocm_mesh *m, c
 static int barrier_run(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs, size_t nee,
                        float dHat, float kappa, int mollify, const int *starts, const int *entries, float *scratch, float *ptEnergy,
                        float *eeEnergy, double *total, float *grad, int *status) {
-  if (!pol || !m || !m->stats || !(dHat > 0.f && dHat <= FLT_MAX) || !(kappa > 0.f && kappa <= FLT_MAX) || (mollify && !m->hasRest)) return -1;
-  if (!barrier_counts_ok(npt, nee) || (npt && !ptPairs) || (nee && !eePairs)) return -1;
+  if (!barrier_args_ok(pol, m, ptPairs, npt, eePairs, nee, dHat, kappa, mollify)) return -1;
   if (grad && m->nv && (!starts || (npt + nee && (!entries || !scratch)))) return -1;
   Launch L(pol, grad ? "mesh_barrier_gradient" : "mesh_barrier_energy");
-  const float *x = verts ? verts : m->verts;
-  const float dHat2 = dHat * dHat;
-  int *st = status ? status : (int *)L.temp(sizeof(int) * 2);
-  ZSR_CHECK(hipMemsetAsync(st, 0, sizeof(int) * 2, L.stream));
   if (npt && !ptEnergy) ptEnergy = (float *)L.temp(sizeof(float) * npt);
   if (nee && !eeEnergy) eeEnergy = (float *)L.temp(sizeof(float) * nee);
-  if (npt) {
-    const dim3 grid(ceil_div(npt, BAR_BLOCK)), block(BAR_BLOCK);
-    if (grad)
-      hipLaunchKernelGGL((barrier_pt_kernel<true>), grid, block, 0, L.stream, x, m->tris, (int)m->nv, (int)m->nt, ptPairs, (int)npt, dHat2, kappa,
-                         ptEnergy, scratch, st);
-    else
-      hipLaunchKernelGGL((barrier_pt_kernel<false>), grid, block, 0, L.stream, x, m->tris, (int)m->nv, (int)m->nt, ptPairs, (int)npt, dHat2, kappa,
-                         ptEnergy, (float *)nullptr, st);
-  }
-  if (nee) {
-    const dim3 grid(ceil_div(nee, BAR_BLOCK)), block(BAR_BLOCK);
-    const float *rest = mollify ? m->restLen2 : nullptr;
-    float *out = grad ? scratch + 12 * npt : nullptr;
-    if (grad)
-      hipLaunchKernelGGL((barrier_ee_kernel<true>), grid, block, 0, L.stream, x, m->edges, (int)m->nv, (int)m->ne, rest, eePairs, (int)nee, dHat2,
-                         kappa, eeEnergy, out, st);
-    else
-      hipLaunchKernelGGL((barrier_ee_kernel<false>), grid, block, 0, L.stream, x, m->edges, (int)m->nv, (int)m->ne, rest, eePairs, (int)nee, dHat2,
-                         kappa, eeEnergy, out, st);
-  }
+  barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, grad ? BARRIER_OP_GRADIENT : BARRIER_OP_ENERGY, nullptr,
+                       ptEnergy, eeEnergy, grad ? scratch : nullptr, status);
   if (total) {
     const size_t n = npt + nee, parts = (n + RED_CHUNK - 1) / RED_CHUNK;
     double *partial = parts ? (double *)L.temp(sizeof(double) * parts) : nullptr;
@@ -346,33 +317,11 @@ int zs_rocm_mesh_barrier_gradient(zs_rocm_policy *pol, const zs_rocm_mesh *m, co
 int zs_rocm_mesh_barrier_hessian_product(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt,
                                          const int *eePairs, size_t nee, float dHat, float kappa, int mollify, int psd, const float *x,
                                          const int *starts, const int *entries, float *scratch, float *hx, int *status) {
-  if (!pol || !m || !m->stats || !(dHat > 0.f && dHat <= FLT_MAX) || !(kappa > 0.f && kappa <= FLT_MAX) || (mollify && !m->hasRest)) return -1;
-  if (!barrier_counts_ok(npt, nee) || (npt && !ptPairs) || (nee && !eePairs)) return -1;
+  if (!barrier_args_ok(pol, m, ptPairs, npt, eePairs, nee, dHat, kappa, mollify)) return -1;
   if (m->nv && (!x || !hx || !starts || (npt + nee && (!entries || !scratch)))) return -1;
   Launch L(pol, "mesh_barrier_hessian_product");
-  const float *pos = verts ? verts : m->verts;
-  const float dHat2 = dHat * dHat;
-  int *st = status ? status : (int *)L.temp(sizeof(int) * 2);
-  ZSR_CHECK(hipMemsetAsync(st, 0, sizeof(int) * 2, L.stream));
-  if (npt) {
-    const dim3 grid(ceil_div(npt, BAR_BLOCK)), block(BAR_BLOCK);
-    if (psd)
-      hipLaunchKernelGGL((barrier_pt_hvp_kernel<true>), grid, block, 0, L.stream, pos, m->tris, (int)m->nv, (int)m->nt, ptPairs, (int)npt, dHat2,
-                         kappa, x, scratch, st);
-    else
-      hipLaunchKernelGGL((barrier_pt_hvp_kernel<false>), grid, block, 0, L.stream, pos, m->tris, (int)m->nv, (int)m->nt, ptPairs, (int)npt, dHat2,
-                         kappa, x, scratch, st);
-  }
-  if (nee) {
-    const dim3 grid(ceil_div(nee, BAR_BLOCK)), block(BAR_BLOCK);
-    const float *rest = mollify ? m->restLen2 : nullptr;
-    if (psd)
-      hipLaunchKernelGGL((barrier_ee_hvp_kernel<true>), grid, block, 0, L.stream, pos, m->edges, (int)m->nv, (int)m->ne, rest, eePairs, (int)nee,
-                         dHat2, kappa, x, scratch + 12 * npt, st);
-    else
-      hipLaunchKernelGGL((barrier_ee_hvp_kernel<false>), grid, block, 0, L.stream, pos, m->edges, (int)m->nv, (int)m->ne, rest, eePairs, (int)nee,
-                         dHat2, kappa, x, scratch + 12 * npt, st);
-  }
+  barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, psd ? BARRIER_OP_PRODUCT_PSD : BARRIER_OP_PRODUCT, x, nullptr,
+                       nullptr, scratch, status);
   if (m->nv)
     hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
                        hx);

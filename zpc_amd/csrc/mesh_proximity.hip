@@ -27,9 +27,6 @@
 
 namespace zsr {
 
-void exclusive_scan_u32(Launch &L, const unsigned *in, size_t n, unsigned *out);
-void radix_sort_pair_u32(Launch &L, const unsigned *kin, const int *vin, unsigned *kout, int *vout, size_t n, int sbit, int ebit);
-
 constexpr int PROX_BLOCK = 64, PROX_QUEUE = 128;  // a push adds at most 64 entries to fewer than 64 waiting ones
 constexpr int PROX_CACHE = 32;                    // cached hit candidates per owner (128 bytes per vertex / edge)
 

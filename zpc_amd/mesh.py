@@ -39,6 +39,10 @@ def _dev_f32(a, cols):
     return t
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 class _ProximityState:
     """room on a Proximity for what the library keeps with it (the incidence of TriMesh.barrier), next to its public fields"""
 
@@ -221,35 +225,45 @@ class TriMesh:
             prox._incidence = (starts, entries, int(sizes[2]))
         return prox._incidence
 
+    def _barrier_args(self, who, prox, dhat, kappa, verts, mollify):
+        """what barrier and barrier_hessian_product (who, for the messages) share: the arguments checked; returns the trial positions or None,
+        the contiguous lists, their counts and the head of the C call up to mollify"""
+        dhat, kappa = float(dhat), float(kappa)
+        for name, x in (("dhat", dhat), ("kappa", kappa)):
+            if not (np.isfinite(x) and x > 0 and np.float32(x) > 0 and np.isfinite(np.float32(x))):
+                raise ValueError("TriMesh.%s: %s must be finite and positive" % (who, name))
+        if mollify and not getattr(self, "has_rest", False):
+            raise ValueError("TriMesh.%s: mollify=True needs the rest lengths, call set_rest first" % who)
+        if not isinstance(prox, Proximity):
+            raise ValueError("TriMesh.%s: prox is the result of TriMesh.proximity" % who)
+        v = None if verts is None else _dev_f32(verts, 3)
+        if v is not None and v.shape[0] != self.nv:
+            raise ValueError("TriMesh.%s: verts are [nv, 3] positions on the same topology" % who)
+        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
+        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
+        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+        return v, pt, ee, npt, nee, (self.pol.handle, self._h, _ptr(v), _ptr(pt), npt, _ptr(ee), nee, dhat, kappa, 1 if mollify else 0)
+
+    def _zero_distance(self, status):
+        """waits for the call and returns the (PT, EE) pairs it counted at zero distance"""
+        self.pol.syncCtx()
+        z = status.tolist()
+        return int(z[0]), int(z[1])
+
     def barrier(self, prox, dhat, kappa, verts=None, mollify=True, gradient=True):
         """the IPC barrier potential -kappa (d2 - dhat^2)^2 log(d2 / dhat^2) summed over the pairs of prox (a Proximity of this mesh; a side
         that is None is skipped), and its gradient: a Barrier.  verts [nv, 3]: trial positions on the same topology instead of the mesh's
         own; distances are recomputed there, the lists stay as they are.  mollify: edge-edge pairs are multiplied by the mollifier of
         nearly parallel edges, which needs set_rest.  Two calls give the same bytes."""
         import torch
-        dhat, kappa = float(dhat), float(kappa)
-        for name, x in (("dhat", dhat), ("kappa", kappa)):
-            if not (np.isfinite(x) and x > 0 and np.float32(x) > 0 and np.isfinite(np.float32(x))):
-                raise ValueError("TriMesh.barrier: %s must be finite and positive" % name)
-        if mollify and not getattr(self, "has_rest", False):
-            raise ValueError("TriMesh.barrier: mollify=True needs the rest lengths, call set_rest first")
-        if not isinstance(prox, Proximity):
-            raise ValueError("TriMesh.barrier: prox is the result of TriMesh.proximity")
-        v = None if verts is None else _dev_f32(verts, 3)
-        if v is not None and v.shape[0] != self.nv:
-            raise ValueError("TriMesh.barrier: verts are [nv, 3] positions on the same topology")
-        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
-        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
-        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+        v, pt, ee, npt, nee, head = self._barrier_args("barrier", prox, dhat, kappa, verts, mollify)
         r = Barrier()
         r.energy = torch.empty((), dtype=torch.float64, device="cuda")
         r.pt_energy = None if pt is None else torch.empty(npt, dtype=torch.float32, device="cuda")
         r.ee_energy = None if ee is None else torch.empty(nee, dtype=torch.float32, device="cuda")
         r.grad = None
         status = torch.empty(2, dtype=torch.int32, device="cuda")
-        ptr = lambda t: None if t is None else t.data_ptr()
-        head = (self.pol.handle, self._h, ptr(v), ptr(pt), npt, ptr(ee), nee, dhat, kappa, 1 if mollify else 0)
-        tail = (ptr(r.pt_energy), ptr(r.ee_energy), r.energy.data_ptr())
+        tail = (_ptr(r.pt_energy), _ptr(r.ee_energy), r.energy.data_ptr())
         if gradient:
             starts, entries, nscratch = self._incidence(prox, pt, ee)
             scratch = torch.empty(nscratch, dtype=torch.float32, device="cuda")
@@ -260,9 +274,7 @@ class TriMesh:
             rc = lib().zs_rocm_mesh_barrier_energy(*head, *tail, status.data_ptr())
         if rc != 0:
             raise RuntimeError("the barrier call failed")
-        self.pol.syncCtx()
-        z = status.tolist()
-        r.zero_distance = (int(z[0]), int(z[1]))
+        r.zero_distance = self._zero_distance(status)
         return r
 
     def barrier_hessian_product(self, prox, dhat, kappa, x, verts=None, mollify=True, psd=False):
@@ -271,36 +283,19 @@ class TriMesh:
         analytically; a majorant of H without the mollifier, not the eigenvalue projection of the per-pair blocks), the operator a
         conjugate-gradient solve can use.  Two calls give the same bytes."""
         import torch
-        dhat, kappa = float(dhat), float(kappa)
-        for name, val in (("dhat", dhat), ("kappa", kappa)):
-            if not (np.isfinite(val) and val > 0 and np.float32(val) > 0 and np.isfinite(np.float32(val))):
-                raise ValueError("TriMesh.barrier_hessian_product: %s must be finite and positive" % name)
-        if mollify and not getattr(self, "has_rest", False):
-            raise ValueError("TriMesh.barrier_hessian_product: mollify=True needs the rest lengths, call set_rest first")
-        if not isinstance(prox, Proximity):
-            raise ValueError("TriMesh.barrier_hessian_product: prox is the result of TriMesh.proximity")
-        v = None if verts is None else _dev_f32(verts, 3)
-        if v is not None and v.shape[0] != self.nv:
-            raise ValueError("TriMesh.barrier_hessian_product: verts are [nv, 3] positions on the same topology")
+        v, pt, ee, npt, nee, head = self._barrier_args("barrier_hessian_product", prox, dhat, kappa, verts, mollify)
         d = _dev_f32(x, 3)
         if d.shape[0] != self.nv:
             raise ValueError("TriMesh.barrier_hessian_product: x is an [nv, 3] direction")
-        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
-        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
-        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
         starts, entries, nscratch = self._incidence(prox, pt, ee)
         r = BarrierHessianProduct()
         r.pair_terms = torch.empty(nscratch // 12, 4, 3, dtype=torch.float32, device="cuda")
         r.hx = torch.empty(self.nv, 3, dtype=torch.float32, device="cuda")
         status = torch.empty(2, dtype=torch.int32, device="cuda")
-        ptr = lambda t: None if t is None else t.data_ptr()
-        if lib().zs_rocm_mesh_barrier_hessian_product(self.pol.handle, self._h, ptr(v), ptr(pt), npt, ptr(ee), nee, dhat, kappa, 1 if mollify else 0,
-                                                      1 if psd else 0, d.data_ptr(), starts.data_ptr(), entries.data_ptr(),
+        if lib().zs_rocm_mesh_barrier_hessian_product(*head, 1 if psd else 0, d.data_ptr(), starts.data_ptr(), entries.data_ptr(),
                                                       r.pair_terms.data_ptr(), r.hx.data_ptr(), status.data_ptr()) != 0:
             raise RuntimeError("the barrier Hessian product call failed")
-        self.pol.syncCtx()
-        z = status.tolist()
-        r.zero_distance = (int(z[0]), int(z[1]))
+        r.zero_distance = self._zero_distance(status)
         return r
 
     @staticmethod
