@@ -898,6 +898,19 @@ ZS_ROCM_EXPORT int zs_rocm_mesh_barrier_hessian_product(zs_rocm_policy *, const 
                                                         const int *eePairs, size_t nee, float dHat, float kappa, int mollify, int psd,
                                                         const float *x, const int *starts, const int *entries, float *scratch, float *hx,
                                                         int *status);
+/* ---- mesh CCD (zpc_amd/csrc/mesh_ccd.hip, include/zensim_rocm/ccd_device.hpp): a conservative bound on the step t in [0, tMax] for which
+ * verts + t dir (verts NULL: the mesh's own positions; dir [nv][3]) keeps every pair of the two lists free of contact, by additive CCD on
+ * the unsigned distance -- what a line search needs before it may evaluate the barrier.  The reference has yes / no tests only
+ * (vertexFaceCCD / edgeEdgeCCD, geometry/Geometry.hpp; pt_ccd_broadphase / ee_ccd_broadphase, geometry/AnalyticLevelSet.h).  Per pair the
+ * step keeps the distance above slack x its value at t = 0; ptToi [npt] / eeToi [nee] receive the per-pair bounds (NULL: not wanted), tMin
+ * (one device float) their minimum and tMax, status int[4] = the pairs at zero distance PT, EE (their bound is 0), then the pairs stopped
+ * by maxIter distance evaluations PT, EE (their bound is valid, not tight).  A pair with an index outside the mesh gets tMax, a pair with a
+ * NaN or Inf in its rows 0.  Two calls give the same bytes; the outputs do not depend on the order of the lists.  -1 and nothing written
+ * for a NULL policy, mesh, dir or tMin, slack outside (0, 1), a tMax that is not finite and positive, maxIter < 1, a list with a count
+ * and no pointer, or 2^28 pairs and more; with both lists empty tMin = tMax. */
+ZS_ROCM_EXPORT int zs_rocm_mesh_ccd(zs_rocm_policy *, const zs_rocm_mesh *, const float *verts, const float *dir, const int *ptPairs, size_t npt,
+                                    const int *eePairs, size_t nee, float slack, float tMax, int maxIter, float *ptToi, float *eeToi,
+                                    float *tMin, int *status);
 /* ---- slotted particle storage: the motion-robust form of the fused step (zpc_amd/csrc/mpm_slotted.hip).  Storage = bins x K rounds x
  * 64 lanes in ONE TileVector<f32, 64> (slot (bin, r, lane) = element (bin K + r) 64 + lane), cellMask[bin][lane] = occupied rounds of the
  * cell; a particle is always stored under the cell of its base node, and the step keeps it so.  A particle that changes cell is finished

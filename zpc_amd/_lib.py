@@ -479,9 +479,10 @@ def _declare_containers(L):
     L.zs_rocm_mesh_barrier_energy.argtypes = [vp, vp, vp, vp, sz, vp, sz, f32, f32, i32, vp, vp, vp, vp]
     L.zs_rocm_mesh_barrier_gradient.argtypes = [vp, vp, vp, vp, sz, vp, sz, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.zs_rocm_mesh_barrier_hessian_product.argtypes = [vp, vp, vp, vp, sz, vp, sz, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.zs_rocm_mesh_ccd.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, f32, f32, i32, vp, vp, vp, vp]
     for name in ("refit", "total_box", "closest_point", "signed_distance", "levelset_candidates", "levelset_blocks", "levelset_gather", "edges",
                  "proximity_pt_count", "proximity_pt_fill", "proximity_ee_count", "proximity_ee_fill", "set_rest", "rest", "barrier_sizes",
-                 "barrier_incidence", "barrier_energy", "barrier_gradient", "barrier_hessian_product"):
+                 "barrier_incidence", "barrier_energy", "barrier_gradient", "barrier_hessian_product", "ccd"):
         getattr(L, "zs_rocm_mesh_" + name).restype = i32
     L.zs_rocm_dof_assign.argtypes = [vp, vp, vp, sz]
     L.zs_rocm_dof_assign.restype = None

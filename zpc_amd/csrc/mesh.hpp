@@ -1,5 +1,6 @@
 // mesh.hpp -- the triangle-mesh object of the C ABI, shared by mesh.hip (colliders, mesh -> level set), mesh_proximity.hip (the
-// point-triangle and edge-edge pairs within a contact distance) and mesh_barrier.hip (the contact potential on those pairs).
+// point-triangle and edge-edge pairs within a contact distance), mesh_barrier.hip (the contact potential on those pairs) and mesh_ccd.hip
+// (the largest step along a direction that keeps those pairs apart).
 #pragma once
 #include "common.hpp"
 #include "../../include/zensim_rocm/mesh_device.hpp"
@@ -56,6 +57,35 @@ namespace zsr {
 // primitives.hip
 void exclusive_scan_u32(Launch &L, const unsigned *in, size_t n, unsigned *out);
 void radix_sort_pair_u32(Launch &L, const unsigned *kin, const int *vin, unsigned *kout, int *vout, size_t n, int sbit, int ebit);
+
+// what the kernels over a proximity list (mesh_barrier.hip, mesh_ccd.hip) share: the four corner vertices of pair i of a list pairs [n][2]
+// -- (vertex, triangle) against prims = tris [np][3], or (edge, edge) against prims = edges [np][2] -- false: an index outside the mesh, the
+// pair is inactive.  Every load sits behind the check of its index; an edge's own two vertices are not checked (the mesh's own edge list:
+// they are inside the mesh)
+template <bool EE>
+__device__ __forceinline__ bool pair_corners(const int *pairs, const int *prims, int nv, int np, int i, int (&idx)[4]) {
+  const int p = pairs[2 * (size_t)i], q = pairs[2 * (size_t)i + 1];
+  if constexpr (EE) {
+    if (!((unsigned)p < (unsigned)np && (unsigned)q < (unsigned)np)) return false;
+    idx[0] = prims[2 * (size_t)p], idx[1] = prims[2 * (size_t)p + 1], idx[2] = prims[2 * (size_t)q], idx[3] = prims[2 * (size_t)q + 1];
+    return true;
+  } else {
+    if (!((unsigned)p < (unsigned)nv && (unsigned)q < (unsigned)np)) return false;
+    idx[0] = p, idx[1] = prims[3 * (size_t)q], idx[2] = prims[3 * (size_t)q + 1], idx[3] = prims[3 * (size_t)q + 2];
+    return (unsigned)idx[1] < (unsigned)nv && (unsigned)idx[2] < (unsigned)nv && (unsigned)idx[3] < (unsigned)nv;
+  }
+}
+
+// rows idx of an [nv][3] array
+__device__ __forceinline__ void pair_rows(const float *__restrict__ src, const int (&idx)[4], float (&out)[4][3]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) out[k][d] = src[3 * (size_t)idx[k] + d];
+}
+
+// 4 (npt + nee) incidence entries are ints and go through one radix sort call
+inline bool barrier_counts_ok(size_t npt, size_t nee) { return npt + nee < ((size_t)1 << 28); }
 
 // mesh_proximity.hip: after new vertex positions -- the packed nodes are stale, the edge tree (if built) is refitted; -1 on failure
 int mesh_proximity_refit(zs_rocm_policy *pol, zs_rocm_mesh &m);

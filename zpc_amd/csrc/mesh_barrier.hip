@@ -57,29 +57,14 @@ struct BarrierPairs {
   int *status;              // [2] zero-distance counts, PT then EE
 };
 
-// the four corner vertices of pair i and the mollifier threshold (0: none); false: an index outside the mesh, the pair is inactive.  Every
-// load sits behind the check of its index; an edge's own two vertices are not checked (the mesh's own edge list: they are inside the mesh)
+// the four corner vertices of pair i (pair_corners of mesh.hpp; false: the pair is inactive) and the mollifier threshold (0: none)
 template <bool EE>
 __device__ __forceinline__ bool barrier_corners(const BarrierPairs &a, int i, int (&idx)[4], float &eps) {
-  const int p = a.pairs[2 * (size_t)i], q = a.pairs[2 * (size_t)i + 1];
   eps = 0.f;
-  if constexpr (EE) {
-    if (!((unsigned)p < (unsigned)a.np && (unsigned)q < (unsigned)a.np)) return false;
-    idx[0] = a.prims[2 * (size_t)p], idx[1] = a.prims[2 * (size_t)p + 1], idx[2] = a.prims[2 * (size_t)q], idx[3] = a.prims[2 * (size_t)q + 1];
-    if (a.rest) eps = barrier_ee_eps(a.rest[p], a.rest[q]);
-    return true;
-  } else {
-    if (!((unsigned)p < (unsigned)a.nv && (unsigned)q < (unsigned)a.np)) return false;
-    idx[0] = p, idx[1] = a.prims[3 * (size_t)q], idx[2] = a.prims[3 * (size_t)q + 1], idx[3] = a.prims[3 * (size_t)q + 2];
-    return (unsigned)idx[1] < (unsigned)a.nv && (unsigned)idx[2] < (unsigned)a.nv && (unsigned)idx[3] < (unsigned)a.nv;
-  }
-}
-
-__device__ __forceinline__ void barrier_rows(const float *__restrict__ src, const int (&idx)[4], float (&out)[4][3]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) out[k][d] = src[3 * (size_t)idx[k] + d];
+  if (!pair_corners<EE>(a.pairs, a.prims, a.nv, a.np, i, idx)) return false;
+  if constexpr (EE)
+    if (a.rest) eps = barrier_ee_eps(a.rest[a.pairs[2 * (size_t)i]], a.rest[a.pairs[2 * (size_t)i + 1]]);
+  return true;
 }
 
 template <bool EE, int OP>
@@ -91,11 +76,11 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_pair_kernel(const BarrierPa
   float eps, e = 0.f, g[4][3] = {};
   if (barrier_corners<EE>(a, i, idx, eps)) {
     float p[4][3];
-    barrier_rows(a.verts, idx, p);
+    pair_rows(a.verts, idx, p);
     int status;
     if constexpr (PRODUCT) {
       float x[4][3];
-      barrier_rows(a.dir, idx, x);
+      pair_rows(a.dir, idx, x);
       if constexpr (EE)
         status = barrier_ee_hvp<OP == BARRIER_OP_PRODUCT_PSD>(p[0], p[1], p[2], p[3], x, a.dHat2, a.kappa, eps, g);
       else
@@ -179,8 +164,6 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_gather_kernel(const int *__
   grad[3 * (size_t)v + 1] = s1;
   grad[3 * (size_t)v + 2] = s2;
 }
-
-static bool barrier_counts_ok(size_t npt, size_t nee) { return npt + nee < ((size_t)1 << 28); }  // 4 (npt + nee) entries: ints, and one radix sort call
 
 // the checks the energy, the gradient and the product have in common
 static bool barrier_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const int *ptPairs, size_t npt, const int *eePairs, size_t nee,

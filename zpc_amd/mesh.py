@@ -1,6 +1,7 @@
 """Triangle meshes as colliders: TriMesh owns a device mesh object of the library (LBvh over the triangle boxes, face normals, vertex and
 edge pseudonormals) and answers closest-point and signed-distance queries and the proximity pairs of the mesh with itself (vertex-triangle and edge-edge within a
-contact distance) and the IPC barrier potential with its gradient and Hessian-vector product on those pairs; SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
+contact distance), the IPC barrier potential with its gradient and Hessian-vector product on those pairs and the largest step along a
+direction that keeps them apart (max_step, step_candidates); SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
 into a sparse level set.  Set-up code: torch for the plumbing; every query runs in the library's HIP kernels."""
 import ctypes as C
 
@@ -28,6 +29,31 @@ def candidate_capacity(pairs, box_lo, box_hi, origin, voxel, band):
     hi = np.ceil((np.asarray(box_hi, np.float64) - np.asarray(origin, np.float64) + band) / voxel) + 2
     nb = np.floor(hi / 8) - np.floor(lo / 8) + 1
     return int(max(1, min(float(pairs), float(np.prod(nb)))))
+
+
+def proximity_grey(r, box_lo, box_hi):
+    """upper bound for the grey zone of the float32 proximity test at radius r on a mesh inside the box: a pair is listed when its float32
+    distance is below r, and that distance is off by at most 64 u (S + M), u = 2^-24, S = distance + the lengths of two edges (at most
+    the box diagonal each), M = the largest coordinate (the derivation is with the distance code; 64 is the edge-edge constant, the
+    point-triangle one is 32).  Host logic."""
+    lo, hi = np.asarray(box_lo, np.float64), np.asarray(box_hi, np.float64)
+    diag = float(np.linalg.norm(hi - lo)) if lo.size else 0.0
+    big = float(max(np.abs(lo).max(), np.abs(hi).max())) if lo.size else 0.0
+    return 2.0 ** -18 * (float(r) + 2.0 * diag + big) + 1e-37
+
+
+def candidate_radius(max_norm, t_max, margin, box_lo, box_hi):
+    """radius of TriMesh.step_candidates: 2 t_max max|direction| + margin plus the grey zone of the proximity test at that radius, as a
+    float32 number rounded up.  max_norm is the largest float32 row norm (4 roundings below the exact one at most: raised by 8 u).  With
+    margin=None the margin is the grey zone once more.  Host logic, float64."""
+    reach = 2.0 * float(t_max) * float(max_norm) * (1.0 + 2.0 ** -21)
+    # the grey zone g at the radius it leads to: g = c (reach + margin + g + ..), c = 2^-18, so at most 1 / (1 - 2 c) of the zone without it
+    grey = proximity_grey(reach + (0.0 if margin is None else float(margin)), box_lo, box_hi) * (1.0 + 2.0 ** -16)
+    r = reach + (grey if margin is None else float(margin)) + grey
+    r32 = np.float32(r)
+    if float(r32) < r:
+        r32 = np.nextafter(r32, np.float32(np.inf))
+    return float(r32)
 
 
 def _dev_f32(a, cols):
@@ -71,6 +97,13 @@ class BarrierHessianProduct:
     (H_pair x) on each pair's four corners, PT pairs first: the scratch of the call), zero_distance = (PT, EE) pairs that contribute
     nothing because their distance is zero"""
     __slots__ = ("hx", "pair_terms", "zero_distance")
+
+
+class StepBound:
+    """result of TriMesh.max_step: t (float32 device scalar: the largest step every pair allows, at most t_max), pt_toi [npt], ee_toi [nee]
+    (the per-pair bounds, None for a side the Proximity does not have), zero_distance = (PT, EE) pairs that start at zero distance (their
+    bound is 0), capped = (PT, EE) pairs stopped by max_iter (their bound is valid, not tight)"""
+    __slots__ = ("t", "pt_toi", "ee_toi", "zero_distance", "capped")
 
 
 class TriMesh:
@@ -297,6 +330,77 @@ class TriMesh:
             raise RuntimeError("the barrier Hessian product call failed")
         r.zero_distance = self._zero_distance(status)
         return r
+
+    def _direction(self, who, direction):
+        d = _dev_f32(direction, 3)
+        if d.shape[0] != self.nv:
+            raise ValueError("TriMesh.%s: direction is an [nv, 3] array" % who)
+        return d
+
+    def max_step(self, prox, direction, verts=None, slack=0.1, t_max=1.0, max_iter=256):
+        """a conservative bound on the step t <= t_max for which verts + t direction (verts=None: the mesh's own positions) keeps every
+        pair of prox (a Proximity of this mesh; a side that is None is skipped) free of contact, by additive CCD: a StepBound.  Each pair
+        keeps its distance above slack x its distance at t = 0; max_iter caps the distance evaluations of one pair.  Only the pairs of
+        prox are looked at: step_candidates gives a list that is complete for a direction.  Two calls give the same bytes."""
+        import torch
+        slack, t_max = float(slack), float(t_max)
+        if not (0.0 < slack < 1.0 and 0.0 < float(np.float32(slack)) < 1.0):
+            raise ValueError("TriMesh.max_step: slack must be inside (0, 1)")
+        if not (np.isfinite(t_max) and t_max > 0 and np.float32(t_max) > 0 and np.isfinite(np.float32(t_max))):
+            raise ValueError("TriMesh.max_step: t_max must be finite and positive")
+        if int(max_iter) != max_iter or max_iter < 1 or max_iter > 2 ** 31 - 1:
+            raise ValueError("TriMesh.max_step: max_iter is an integer of at least 1")
+        if not isinstance(prox, Proximity):
+            raise ValueError("TriMesh.max_step: prox is the result of TriMesh.proximity or TriMesh.step_candidates")
+        d = self._direction("max_step", direction)
+        v = None if verts is None else _dev_f32(verts, 3)
+        if v is not None and v.shape[0] != self.nv:
+            raise ValueError("TriMesh.max_step: verts are [nv, 3] positions on the same topology")
+        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
+        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
+        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+        r = StepBound()
+        r.t = torch.empty((), dtype=torch.float32, device="cuda")
+        r.pt_toi = None if pt is None else torch.empty(npt, dtype=torch.float32, device="cuda")
+        r.ee_toi = None if ee is None else torch.empty(nee, dtype=torch.float32, device="cuda")
+        status = torch.empty(4, dtype=torch.int32, device="cuda")
+        if lib().zs_rocm_mesh_ccd(self.pol.handle, self._h, _ptr(v), d.data_ptr(), _ptr(pt), npt, _ptr(ee), nee, slack, t_max, int(max_iter),
+                                  _ptr(r.pt_toi), _ptr(r.ee_toi), r.t.data_ptr(), status.data_ptr()) != 0:
+            raise RuntimeError("the CCD call failed")
+        self.pol.syncCtx()
+        s = status.tolist()
+        r.zero_distance, r.capped = (int(s[0]), int(s[1])), (int(s[2]), int(s[3]))
+        return r
+
+    def step_candidates(self, direction, t_max=1.0, margin=None):
+        """the pairs max_step has to look at for steps up to t_max along direction [nv, 3], from the mesh's own positions: self.proximity(r)
+        with r = 2 t_max max|direction| + margin + the grey zone of the proximity test, rounded up (candidate_radius).  Complete: over a
+        step t <= t_max no vertex moves further than t_max max|direction|, so the distance of a pair falls by at most 2 t_max
+        max|direction|; a pair that is not listed has a float32 distance of at least r, a true one of at least r minus the grey zone, and
+        keeps at least margin over the whole step.  margin=None: the grey zone once more.  As in every proximity list, topological
+        neighbours (a triangle that contains the vertex, edges that share a vertex) are not listed: their distance is zero by
+        construction and stays so.  An all-zero direction (or a mesh without triangles) gives an empty Proximity."""
+        import torch
+        d = self._direction("step_candidates", direction)
+        t_max = float(t_max)
+        if not (np.isfinite(t_max) and t_max > 0):
+            raise ValueError("TriMesh.step_candidates: t_max must be finite and positive")
+        if margin is not None and not (np.isfinite(margin) and margin >= 0):
+            raise ValueError("TriMesh.step_candidates: margin must be finite and not negative")
+        top = float(torch.linalg.vector_norm(d, dim=1).max().item()) if self.nv else 0.0
+        if not np.isfinite(top):
+            raise ValueError("TriMesh.step_candidates: direction must be finite")
+        if top == 0.0 or self.nt == 0:
+            r = Proximity()
+            i32, f32 = dict(dtype=torch.int32, device="cuda"), dict(dtype=torch.float32, device="cuda")
+            r.pt_pairs, r.pt_dist2, r.pt_feature, r.pt_bary = torch.empty(0, 2, **i32), torch.empty(0, **f32), torch.empty(0, **i32), torch.empty(0, 3, **f32)
+            r.ee_pairs, r.ee_dist2, r.ee_category, r.ee_st = torch.empty(0, 2, **i32), torch.empty(0, **f32), torch.empty(0, **i32), torch.empty(0, 2, **f32)
+            return r
+        lo, hi = self.total_box()
+        radius = candidate_radius(top, t_max, margin, lo, hi)
+        if not np.isfinite(radius):
+            raise ValueError("TriMesh.step_candidates: 2 t_max max|direction| + margin leaves the float range")
+        return self.proximity(radius)
 
     @staticmethod
     def _cap(cap):
