@@ -898,6 +898,37 @@ ZS_ROCM_EXPORT int zs_rocm_mesh_barrier_hessian_product(zs_rocm_policy *, const 
                                                         const int *eePairs, size_t nee, float dHat, float kappa, int mollify, int psd,
                                                         const float *x, const int *starts, const int *entries, float *scratch, float *hx,
                                                         int *status);
+/* ---- mesh friction (zpc_amd/csrc/mesh_barrier.hip, include/zensim_rocm/friction_device.hpp): lagged IPC friction over the same PT and EE
+ * lists -- the smoothed static-friction functions f0_SF / f1_SF_div_rel_dx_norm / f2_SF_term and the tangent bases and relative
+ * displacements of geometry/Friction.hpp, with the projector I - n n^T in place of the per-feature bases.
+ *   lag       at verts [nv][3] (NULL: the mesh's own positions), the positions the normal forces are frozen at: record [npt + nee][8]
+ *             floats, PT pairs first, each n[3] (the unit vector P - Q), lambda = m (-b'(d2)) 2 d (the size of the contact force; dHat,
+ *             kappa, mollify as for the barrier) and w[4] (the weights of the relative displacement).  A pair at dHat or beyond, or with
+ *             an index outside the mesh, gets an all-zero record; so does a pair at zero distance or with a lambda beyond the float
+ *             range, which is counted in status int[2] (PT, EE).
+ *   energy    at a displacement u [nv][3] (x - x at the start of the step), with mu >= 0 and the static-friction threshold epsv > 0 in
+ *             displacement units, from the record alone:  mu lambda f0(|ut|), ut the tangential part of sum_k w_k u_k.  ptEnergy [npt],
+ *             eeEnergy [nee], total (one double, PT then EE, the barrier's fixed order); each may be NULL.  status int[2] = the PT and EE
+ *             pairs whose |ut|^2 or result leaves the float range: they contribute exactly zero.
+ *   gradient  the same and grad [nv][3], fully overwritten; starts / entries / scratch as for _barrier_gradient (the same incidence).
+ *   product   hx [nv][3] = H x for a direction x [nv][3], H the second derivative of the energy at u: positive semi-definite by
+ *             construction.  scratch receives the per-pair terms [4][3], PT pairs first.
+ * Two calls give the same bytes (no float atomics).  -1 and nothing written for a NULL policy, mesh, record (with pairs) or u, x, hx, grad
+ * (with vertices), a list with a count and no pointer, 2^28 pairs and more, a mu that is negative or not finite, an epsv that is not finite
+ * and positive, and for the lag step the argument errors of _barrier_energy. */
+ZS_ROCM_EXPORT int zs_rocm_mesh_friction_lag(zs_rocm_policy *, const zs_rocm_mesh *, const float *verts, const int *ptPairs, size_t npt,
+                                             const int *eePairs, size_t nee, float dHat, float kappa, int mollify, float *record, int *status);
+ZS_ROCM_EXPORT int zs_rocm_mesh_friction_energy(zs_rocm_policy *, const zs_rocm_mesh *, const float *u, const int *ptPairs, size_t npt,
+                                                const int *eePairs, size_t nee, const float *record, float mu, float epsv, float *ptEnergy,
+                                                float *eeEnergy, double *total, int *status);
+ZS_ROCM_EXPORT int zs_rocm_mesh_friction_gradient(zs_rocm_policy *, const zs_rocm_mesh *, const float *u, const int *ptPairs, size_t npt,
+                                                  const int *eePairs, size_t nee, const float *record, float mu, float epsv, const int *starts,
+                                                  const int *entries, float *scratch, float *ptEnergy, float *eeEnergy, double *total,
+                                                  float *grad, int *status);
+ZS_ROCM_EXPORT int zs_rocm_mesh_friction_hessian_product(zs_rocm_policy *, const zs_rocm_mesh *, const float *u, const float *x,
+                                                         const int *ptPairs, size_t npt, const int *eePairs, size_t nee, const float *record,
+                                                         float mu, float epsv, const int *starts, const int *entries, float *scratch,
+                                                         float *hx, int *status);
 /* ---- mesh CCD (zpc_amd/csrc/mesh_ccd.hip, include/zensim_rocm/ccd_device.hpp): a conservative bound on the step t in [0, tMax] for which
  * verts + t dir (verts NULL: the mesh's own positions; dir [nv][3]) keeps every pair of the two lists free of contact, by additive CCD on
  * the unsigned distance -- what a line search needs before it may evaluate the barrier.  The reference has yes / no tests only

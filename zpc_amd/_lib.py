@@ -480,6 +480,12 @@ def _declare_containers(L):
     L.zs_rocm_mesh_barrier_gradient.argtypes = [vp, vp, vp, vp, sz, vp, sz, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.zs_rocm_mesh_barrier_hessian_product.argtypes = [vp, vp, vp, vp, sz, vp, sz, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.zs_rocm_mesh_ccd.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, f32, f32, i32, vp, vp, vp, vp]
+    L.zs_rocm_mesh_friction_lag.argtypes = [vp, vp, vp, vp, sz, vp, sz, f32, f32, i32, vp, vp]
+    L.zs_rocm_mesh_friction_energy.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, f32, f32, vp, vp, vp, vp]
+    L.zs_rocm_mesh_friction_gradient.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.zs_rocm_mesh_friction_hessian_product.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, f32, f32, vp, vp, vp, vp, vp]
+    for name in ("friction_lag", "friction_energy", "friction_gradient", "friction_hessian_product"):
+        getattr(L, "zs_rocm_mesh_" + name).restype = i32
     for name in ("refit", "total_box", "closest_point", "signed_distance", "levelset_candidates", "levelset_blocks", "levelset_gather", "edges",
                  "proximity_pt_count", "proximity_pt_fill", "proximity_ee_count", "proximity_ee_fill", "set_rest", "rest", "barrier_sizes",
                  "barrier_incidence", "barrier_energy", "barrier_gradient", "barrier_hessian_product", "ccd"):

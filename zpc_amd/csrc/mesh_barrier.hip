@@ -8,6 +8,10 @@
 //             parameters and feature at the given positions and writes the pair's energy and / or its [4][3] contributions to a scratch
 //             array, once.  Zero-distance pairs are counted with an integer atomic (a count has no order).  A new per-pair quantity is one
 //             more BARRIER_OP_* and its branch in barrier_pair_kernel.
+//   friction  four such operations (include/zensim_rocm/friction_device.hpp has the math).  The lag step runs at positions like the barrier
+//             and writes one 32-byte record (n, lambda, w) per pair, PT pairs first; friction energy, gradient and product gather the
+//             displacement u where the barrier gathers positions, read the record and never touch the distance code.  Their per-pair
+//             energies and [4][3] contributions go through the same sum and the same gather.
 //   energy    float64 sum of the per-pair energies, PT then EE, in a fixed order: workgroup g sums elements [g, g + 1) x RED_CHUNK, thread
 //             t the elements t, t + 256, .. of the chunk, then an LDS tree; one workgroup sums the partials the same way.
 //   incidence built once per pair of lists, independent of the positions: the 4 (npt + nee) (vertex, 4 pair + corner) entries -- EE pairs
@@ -20,6 +24,7 @@
 
 #include "mesh.hpp"
 #include "../../include/zensim_rocm/barrier_device.hpp"
+#include "../../include/zensim_rocm/friction_device.hpp"
 
 namespace zsr {
 
@@ -41,11 +46,32 @@ __device__ __forceinline__ void barrier_store(float *contrib, size_t pair, const
   o[2] = make_float4(g[2][2], g[3][0], g[3][1], g[3][2]);
 }
 
-enum { BARRIER_OP_ENERGY, BARRIER_OP_GRADIENT, BARRIER_OP_PRODUCT, BARRIER_OP_PRODUCT_PSD };
+enum {
+  BARRIER_OP_ENERGY,
+  BARRIER_OP_GRADIENT,
+  BARRIER_OP_PRODUCT,
+  BARRIER_OP_PRODUCT_PSD,
+  BARRIER_OP_LAG,                // friction: the lagged record at verts
+  BARRIER_OP_FRICTION_ENERGY,    // friction at the displacement verts, from the record
+  BARRIER_OP_FRICTION_GRADIENT,
+  BARRIER_OP_FRICTION_PRODUCT
+};
+
+// the friction record of pair i: 32-byte records in a 256-byte aligned array, as two float4
+__device__ __forceinline__ void friction_store(float *record, size_t pair, const FrictionRecord &r) {
+  float4 *o = reinterpret_cast<float4 *>(record + 8 * pair);
+  o[0] = make_float4(r.n[0], r.n[1], r.n[2], r.lambda);
+  o[1] = make_float4(r.w[0], r.w[1], r.w[2], r.w[3]);
+}
+__device__ __forceinline__ FrictionRecord friction_load(const float *record, size_t pair) {
+  const float4 *in = reinterpret_cast<const float4 *>(record + 8 * pair);
+  const float4 a = in[0], b = in[1];
+  return FrictionRecord{{a.x, a.y, a.z}, a.w, {b.x, b.y, b.z, b.w}};
+}
 
 // one pair list of one kind and what the pair kernel reads and writes for it
 struct BarrierPairs {
-  const float *verts;  // [nv][3] positions
+  const float *verts;  // [nv][3] positions; a friction evaluation: the displacement u
   const int *prims;    // the kind's primitives: tris [np][3] (PT) or edges [np][2] (EE)
   int nv, np;
   const float *rest;  // EE: the squared rest lengths [np]; null: unmollified
@@ -54,7 +80,9 @@ struct BarrierPairs {
   float dHat2, kappa;
   const float *dir;         // [nv][3], a product only
   float *energy, *contrib;  // [n] (energy, gradient) and the [n][4][3] records (all but energy)
-  int *status;              // [2] zero-distance counts, PT then EE
+  int *status;              // [2] zero-distance (a friction evaluation: overflow) counts, PT then EE
+  float *record;            // friction: the [n][8] records, written by the lag step and read by the evaluations
+  float mu, epsv;           // a friction evaluation: the coefficient and the static-friction threshold
 };
 
 // the four corner vertices of pair i (pair_corners of mesh.hpp; false: the pair is inactive) and the mollifier threshold (0: none)
@@ -71,14 +99,32 @@ template <bool EE, int OP>
 __global__ __launch_bounds__(BAR_BLOCK) void barrier_pair_kernel(const BarrierPairs a) {
   const int i = blockIdx.x * BAR_BLOCK + threadIdx.x;
   if (i >= a.n) return;
-  constexpr bool PRODUCT = OP == BARRIER_OP_PRODUCT || OP == BARRIER_OP_PRODUCT_PSD;
+  constexpr bool PRODUCT = OP == BARRIER_OP_PRODUCT || OP == BARRIER_OP_PRODUCT_PSD || OP == BARRIER_OP_FRICTION_PRODUCT;
+  constexpr bool FRICTION = OP == BARRIER_OP_FRICTION_ENERGY || OP == BARRIER_OP_FRICTION_GRADIENT || OP == BARRIER_OP_FRICTION_PRODUCT;
   int idx[4];
   float eps, e = 0.f, g[4][3] = {};
+  [[maybe_unused]] FrictionRecord rec = friction_record_zero();
   if (barrier_corners<EE>(a, i, idx, eps)) {
     float p[4][3];
     pair_rows(a.verts, idx, p);
     int status;
-    if constexpr (PRODUCT) {
+    if constexpr (OP == BARRIER_OP_LAG) {
+      if constexpr (EE)
+        status = friction_lag_ee(p[0], p[1], p[2], p[3], a.dHat2, a.kappa, eps, rec);
+      else
+        status = friction_lag_pt(p[0], p[1], p[2], p[3], a.dHat2, a.kappa, rec);
+    } else if constexpr (FRICTION) {
+      rec = friction_load(a.record, (size_t)i);
+      if constexpr (OP == BARRIER_OP_FRICTION_PRODUCT) {
+        float x[4][3];
+        pair_rows(a.dir, idx, x);
+        status = friction_product(rec, p, x, a.mu, a.epsv, g);
+      } else if constexpr (OP == BARRIER_OP_FRICTION_GRADIENT) {
+        status = friction_gradient(rec, p, a.mu, a.epsv, e, g);
+      } else {
+        status = friction_energy(rec, p, a.mu, a.epsv, e);
+      }
+    } else if constexpr (PRODUCT) {
       float x[4][3];
       pair_rows(a.dir, idx, x);
       if constexpr (EE)
@@ -92,8 +138,12 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_pair_kernel(const BarrierPa
     }
     if (status == BARRIER_ZERO) atomicAdd(a.status + EE, 1);
   }
-  if constexpr (!PRODUCT) a.energy[i] = e;
-  if constexpr (OP != BARRIER_OP_ENERGY) barrier_store(a.contrib, (size_t)i, g);
+  if constexpr (OP == BARRIER_OP_LAG) {
+    friction_store(a.record, (size_t)i, rec);
+  } else {
+    if constexpr (!PRODUCT) a.energy[i] = e;
+    if constexpr (OP != BARRIER_OP_ENERGY && OP != BARRIER_OP_FRICTION_ENERGY) barrier_store(a.contrib, (size_t)i, g);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the float64 total
@@ -186,21 +236,47 @@ static void barrier_launch_op(Launch &L, const BarrierPairs &pt, const BarrierPa
   if (ee.n) hipLaunchKernelGGL((barrier_pair_kernel<true, OP>), dim3(ceil_div(ee.n, BAR_BLOCK)), block, 0, L.stream, ee);
 }
 
+// what the friction operations add to a launch: the [npt + nee][8] records (PT pairs first), mu and the threshold
+struct FrictionArgs {
+  float *record;
+  float mu, epsv;
+};
+
 // the pair kernels of one operation: the PT list, then the EE list, whose records follow the PT list's
 static void barrier_launch_pairs(Launch &L, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
                                  size_t nee, float dHat, float kappa, int mollify, int op, const float *dir, float *ptEnergy, float *eeEnergy,
-                                 float *scratch, int *status) {
+                                 float *scratch, int *status, const FrictionArgs &fr = {}) {
   const BarrierPairs pt = {verts ? verts : m->verts, m->tris, (int)m->nv, (int)m->nt, nullptr, ptPairs, (int)npt, dHat * dHat, kappa, dir,
-                           ptEnergy, scratch, barrier_status(L, status)};
+                           ptEnergy, scratch, barrier_status(L, status), fr.record, fr.mu, fr.epsv};
   BarrierPairs ee = pt;
   ee.prims = m->edges, ee.np = (int)m->ne, ee.rest = mollify ? m->restLen2 : nullptr;
   ee.pairs = eePairs, ee.n = (int)nee, ee.energy = eeEnergy, ee.contrib = scratch ? scratch + 12 * npt : nullptr;
+  ee.record = fr.record ? fr.record + 8 * npt : nullptr;
   switch (op) {
     case BARRIER_OP_ENERGY: return barrier_launch_op<BARRIER_OP_ENERGY>(L, pt, ee);
     case BARRIER_OP_GRADIENT: return barrier_launch_op<BARRIER_OP_GRADIENT>(L, pt, ee);
     case BARRIER_OP_PRODUCT: return barrier_launch_op<BARRIER_OP_PRODUCT>(L, pt, ee);
-    default: return barrier_launch_op<BARRIER_OP_PRODUCT_PSD>(L, pt, ee);
+    case BARRIER_OP_PRODUCT_PSD: return barrier_launch_op<BARRIER_OP_PRODUCT_PSD>(L, pt, ee);
+    case BARRIER_OP_LAG: return barrier_launch_op<BARRIER_OP_LAG>(L, pt, ee);
+    case BARRIER_OP_FRICTION_ENERGY: return barrier_launch_op<BARRIER_OP_FRICTION_ENERGY>(L, pt, ee);
+    case BARRIER_OP_FRICTION_GRADIENT: return barrier_launch_op<BARRIER_OP_FRICTION_GRADIENT>(L, pt, ee);
+    default: return barrier_launch_op<BARRIER_OP_FRICTION_PRODUCT>(L, pt, ee);
   }
+}
+
+// the float64 total of the per-pair energies, PT then EE
+static void barrier_launch_total(Launch &L, const float *ptEnergy, size_t npt, const float *eeEnergy, size_t nee, double *total) {
+  const size_t n = npt + nee, parts = (n + RED_CHUNK - 1) / RED_CHUNK;
+  double *partial = parts ? (double *)L.temp(sizeof(double) * parts) : nullptr;
+  if (parts) hipLaunchKernelGGL(barrier_partial_kernel, dim3((unsigned)parts), dim3(BAR_BLOCK), 0, L.stream, ptEnergy, npt, eeEnergy, nee, partial);
+  hipLaunchKernelGGL(barrier_total_kernel, dim3(1), dim3(BAR_BLOCK), 0, L.stream, partial, parts, total);
+}
+
+// the checks the friction evaluations have in common
+static bool friction_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs,
+                             size_t nee, const float *record, float mu, float epsv) {
+  if (!pol || !m || !m->stats || !(mu >= 0.f && mu <= FLT_MAX) || !(epsv > 0.f && epsv <= FLT_MAX) || (m->nv && !u)) return false;
+  return barrier_counts_ok(npt, nee) && !(npt && !ptPairs) && !(nee && !eePairs) && !(npt + nee && !record);
 }
 
 }  // namespace zsr
@@ -270,13 +346,7 @@ static int barrier_run(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *
   if (nee && !eeEnergy) eeEnergy = (float *)L.temp(sizeof(float) * nee);
   barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, grad ? BARRIER_OP_GRADIENT : BARRIER_OP_ENERGY, nullptr,
                        ptEnergy, eeEnergy, grad ? scratch : nullptr, status);
-  if (total) {
-    const size_t n = npt + nee, parts = (n + RED_CHUNK - 1) / RED_CHUNK;
-    double *partial = parts ? (double *)L.temp(sizeof(double) * parts) : nullptr;
-    if (parts)
-      hipLaunchKernelGGL(barrier_partial_kernel, dim3((unsigned)parts), dim3(BAR_BLOCK), 0, L.stream, ptEnergy, npt, eeEnergy, nee, partial);
-    hipLaunchKernelGGL(barrier_total_kernel, dim3(1), dim3(BAR_BLOCK), 0, L.stream, partial, parts, total);
-  }
+  if (total) barrier_launch_total(L, ptEnergy, npt, eeEnergy, nee, total);
   if (grad && m->nv)
     hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
                        grad);
@@ -305,6 +375,61 @@ int zs_rocm_mesh_barrier_hessian_product(zs_rocm_policy *pol, const zs_rocm_mesh
   Launch L(pol, "mesh_barrier_hessian_product");
   barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, psd ? BARRIER_OP_PRODUCT_PSD : BARRIER_OP_PRODUCT, x, nullptr,
                        nullptr, scratch, status);
+  if (m->nv)
+    hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
+                       hx);
+  return 0;
+}
+
+int zs_rocm_mesh_friction_lag(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
+                              size_t nee, float dHat, float kappa, int mollify, float *record, int *status) {
+  if (!barrier_args_ok(pol, m, ptPairs, npt, eePairs, nee, dHat, kappa, mollify) || (npt + nee && !record)) return -1;
+  Launch L(pol, "mesh_friction_lag");
+  barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, BARRIER_OP_LAG, nullptr, nullptr, nullptr, nullptr, status,
+                       {record, 0.f, 0.f});
+  return 0;
+}
+
+// the shared entry: grad == NULL is energy only
+static int friction_run(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs, size_t nee,
+                        const float *record, float mu, float epsv, const int *starts, const int *entries, float *scratch, float *ptEnergy,
+                        float *eeEnergy, double *total, float *grad, int *status) {
+  if (!friction_args_ok(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv)) return -1;
+  if (grad && m->nv && (!starts || (npt + nee && (!entries || !scratch)))) return -1;
+  Launch L(pol, grad ? "mesh_friction_gradient" : "mesh_friction_energy");
+  if (npt && !ptEnergy) ptEnergy = (float *)L.temp(sizeof(float) * npt);
+  if (nee && !eeEnergy) eeEnergy = (float *)L.temp(sizeof(float) * nee);
+  barrier_launch_pairs(L, m, u, ptPairs, npt, eePairs, nee, 0.f, 0.f, 0, grad ? BARRIER_OP_FRICTION_GRADIENT : BARRIER_OP_FRICTION_ENERGY, nullptr,
+                       ptEnergy, eeEnergy, grad ? scratch : nullptr, status, {const_cast<float *>(record), mu, epsv});
+  if (total) barrier_launch_total(L, ptEnergy, npt, eeEnergy, nee, total);
+  if (grad && m->nv)
+    hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
+                       grad);
+  return 0;
+}
+
+int zs_rocm_mesh_friction_energy(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs,
+                                 size_t nee, const float *record, float mu, float epsv, float *ptEnergy, float *eeEnergy, double *total,
+                                 int *status) {
+  return friction_run(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv, nullptr, nullptr, nullptr, ptEnergy, eeEnergy, total, nullptr,
+                      status);
+}
+
+int zs_rocm_mesh_friction_gradient(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs,
+                                   size_t nee, const float *record, float mu, float epsv, const int *starts, const int *entries, float *scratch,
+                                   float *ptEnergy, float *eeEnergy, double *total, float *grad, int *status) {
+  if (!grad && m && m->nv) return -1;
+  return friction_run(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv, starts, entries, scratch, ptEnergy, eeEnergy, total, grad, status);
+}
+
+int zs_rocm_mesh_friction_hessian_product(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const float *x, const int *ptPairs, size_t npt,
+                                          const int *eePairs, size_t nee, const float *record, float mu, float epsv, const int *starts,
+                                          const int *entries, float *scratch, float *hx, int *status) {
+  if (!friction_args_ok(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv)) return -1;
+  if (m->nv && (!x || !hx || !starts || (npt + nee && (!entries || !scratch)))) return -1;
+  Launch L(pol, "mesh_friction_hessian_product");
+  barrier_launch_pairs(L, m, u, ptPairs, npt, eePairs, nee, 0.f, 0.f, 0, BARRIER_OP_FRICTION_PRODUCT, x, nullptr, nullptr, scratch, status,
+                       {const_cast<float *>(record), mu, epsv});
   if (m->nv)
     hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
                        hx);

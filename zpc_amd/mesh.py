@@ -99,6 +99,40 @@ class BarrierHessianProduct:
     __slots__ = ("hx", "pair_terms", "zero_distance")
 
 
+class FrictionLag:
+    """result of TriMesh.friction_lag: record [npt + nee, 8] float32 on the device, PT pairs first, one row per pair of prox; normal
+    [.., 3] (the unit vector between the closest points), lam [..] (the size of the contact force, m (-b') 2 d) and weights [.., 4] (of
+    the relative displacement; they sum to zero) are views of it.  An inactive pair has an all-zero row.  zero_distance = (PT, EE)
+    pairs at zero distance (or with a lam beyond the float range): their row is zero as well.  prox is the Proximity the rows belong to;
+    its incidence is shared with the barrier calls."""
+    __slots__ = ("record", "zero_distance", "prox", "npt", "nee")
+
+    @property
+    def normal(self):
+        return self.record[:, 0:3]
+
+    @property
+    def lam(self):
+        return self.record[:, 3]
+
+    @property
+    def weights(self):
+        return self.record[:, 4:8]
+
+
+class Friction:
+    """result of TriMesh.friction: energy (float64 device scalar: PT then EE, summed in a fixed order), pt_energy [npt], ee_energy [nee]
+    (None for a side the Proximity does not have), grad [nv, 3] or None, overflow = (PT, EE) pairs whose tangential displacement or result
+    leaves the float range (they contribute exactly zero)"""
+    __slots__ = ("energy", "pt_energy", "ee_energy", "grad", "overflow")
+
+
+class FrictionHessianProduct:
+    """result of TriMesh.friction_hessian_product: hx [nv, 3] float32 = H x, pair_terms [npt + nee, 4, 3] float32 (the contributions
+    (H_pair x) on each pair's four corners, PT pairs first: the scratch of the call), overflow as for Friction"""
+    __slots__ = ("hx", "pair_terms", "overflow")
+
+
 class StepBound:
     """result of TriMesh.max_step: t (float32 device scalar: the largest step every pair allows, at most t_max), pt_toi [npt], ee_toi [nee]
     (the per-pair bounds, None for a side the Proximity does not have), zero_distance = (PT, EE) pairs that start at zero distance (their
@@ -329,6 +363,95 @@ class TriMesh:
                                                       r.pair_terms.data_ptr(), r.hx.data_ptr(), status.data_ptr()) != 0:
             raise RuntimeError("the barrier Hessian product call failed")
         r.zero_distance = self._zero_distance(status)
+        return r
+
+    def friction_lag(self, prox, dhat, kappa, verts=None, mollify=True):
+        """the lag step of IPC friction: freezes the contact normal, the size of the contact force and the weights of the relative
+        displacement of every pair of prox at verts [nv, 3] (None: the mesh's own positions): a FrictionLag.  dhat, kappa, mollify as for
+        barrier: the contact force is the barrier's.  Two calls give the same bytes."""
+        import torch
+        v, pt, ee, npt, nee, head = self._barrier_args("friction_lag", prox, dhat, kappa, verts, mollify)
+        sizes = (C.c_size_t * 3)()
+        if lib().zs_rocm_mesh_barrier_sizes(self._h, npt, nee, sizes) != 0:
+            raise ValueError("TriMesh.friction_lag: too many pairs")
+        r = FrictionLag()
+        r.prox, r.npt, r.nee = prox, npt, nee
+        r.record = torch.empty(npt + nee, 8, dtype=torch.float32, device="cuda")
+        status = torch.empty(2, dtype=torch.int32, device="cuda")
+        if lib().zs_rocm_mesh_friction_lag(*head, r.record.data_ptr(), status.data_ptr()) != 0:
+            raise RuntimeError("the friction lag call failed")
+        r.zero_distance = self._zero_distance(status)
+        return r
+
+    def _friction_args(self, who, lag, u, mu, eps_v):
+        """what friction and friction_hessian_product (who, for the messages) share: the arguments checked; returns the displacement, the
+        contiguous lists and the head of the C call up to the pair lists"""
+        mu, eps_v = float(mu), float(eps_v)
+        if not (0 <= mu <= float(np.finfo(np.float32).max)):
+            raise ValueError("TriMesh.%s: mu must be finite and not negative" % who)
+        if not (np.isfinite(eps_v) and eps_v > 0 and np.float32(eps_v) > 0 and np.isfinite(np.float32(eps_v))):
+            raise ValueError("TriMesh.%s: eps_v must be finite and positive" % who)
+        if not isinstance(lag, FrictionLag):
+            raise ValueError("TriMesh.%s: lag is the result of TriMesh.friction_lag" % who)
+        d = _dev_f32(u, 3)
+        if d.shape[0] != self.nv:
+            raise ValueError("TriMesh.%s: u is an [nv, 3] displacement" % who)
+        prox = lag.prox
+        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
+        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
+        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+        rec = lag.record
+        if (npt, nee) != (lag.npt, lag.nee) or tuple(rec.shape) != (npt + nee, 8) or rec.dtype != d.dtype or not rec.is_contiguous():
+            raise ValueError("TriMesh.%s: the lists of lag.prox have changed since friction_lag" % who)
+        return d, pt, ee, npt, nee, mu, eps_v
+
+    def friction(self, lag, u, mu, eps_v, gradient=True):
+        """lagged IPC friction at the displacement u [nv, 3] (positions minus the positions at the start of the step): the energy
+        mu lam f0(|ut|) summed over the pairs of lag (a FrictionLag of this mesh), ut the tangential part of the pair's relative
+        displacement, and its gradient: a Friction.  eps_v: the static-friction threshold in displacement units (the velocity threshold
+        times the time step); below it f0 is the smooth cubic, above it |ut|.  Two calls give the same bytes."""
+        import torch
+        d, pt, ee, npt, nee, mu, eps_v = self._friction_args("friction", lag, u, mu, eps_v)
+        r = Friction()
+        r.energy = torch.empty((), dtype=torch.float64, device="cuda")
+        r.pt_energy = None if pt is None else torch.empty(npt, dtype=torch.float32, device="cuda")
+        r.ee_energy = None if ee is None else torch.empty(nee, dtype=torch.float32, device="cuda")
+        r.grad = None
+        status = torch.empty(2, dtype=torch.int32, device="cuda")
+        head = (self.pol.handle, self._h, d.data_ptr(), _ptr(pt), npt, _ptr(ee), nee, lag.record.data_ptr(), mu, eps_v)
+        tail = (_ptr(r.pt_energy), _ptr(r.ee_energy), r.energy.data_ptr())
+        if gradient:
+            starts, entries, nscratch = self._incidence(lag.prox, pt, ee)
+            scratch = torch.empty(nscratch, dtype=torch.float32, device="cuda")
+            r.grad = torch.empty(self.nv, 3, dtype=torch.float32, device="cuda")
+            rc = lib().zs_rocm_mesh_friction_gradient(*head, starts.data_ptr(), entries.data_ptr(), scratch.data_ptr(), *tail, r.grad.data_ptr(),
+                                                      status.data_ptr())
+        else:
+            rc = lib().zs_rocm_mesh_friction_energy(*head, *tail, status.data_ptr())
+        if rc != 0:
+            raise RuntimeError("the friction call failed")
+        r.overflow = self._zero_distance(status)
+        return r
+
+    def friction_hessian_product(self, lag, u, mu, eps_v, x):
+        """H x for a direction x [nv, 3], H the second derivative of the energy of TriMesh.friction at u, matrix-free: a
+        FrictionHessianProduct.  H is positive semi-definite by construction, so a conjugate-gradient solve can use it as it is.  Two
+        calls give the same bytes."""
+        import torch
+        d, pt, ee, npt, nee, mu, eps_v = self._friction_args("friction_hessian_product", lag, u, mu, eps_v)
+        xd = _dev_f32(x, 3)
+        if xd.shape[0] != self.nv:
+            raise ValueError("TriMesh.friction_hessian_product: x is an [nv, 3] direction")
+        starts, entries, nscratch = self._incidence(lag.prox, pt, ee)
+        r = FrictionHessianProduct()
+        r.pair_terms = torch.empty(nscratch // 12, 4, 3, dtype=torch.float32, device="cuda")
+        r.hx = torch.empty(self.nv, 3, dtype=torch.float32, device="cuda")
+        status = torch.empty(2, dtype=torch.int32, device="cuda")
+        if lib().zs_rocm_mesh_friction_hessian_product(self.pol.handle, self._h, d.data_ptr(), xd.data_ptr(), _ptr(pt), npt, _ptr(ee), nee,
+                                                       lag.record.data_ptr(), mu, eps_v, starts.data_ptr(), entries.data_ptr(),
+                                                       r.pair_terms.data_ptr(), r.hx.data_ptr(), status.data_ptr()) != 0:
+            raise RuntimeError("the friction Hessian product call failed")
+        r.overflow = self._zero_distance(status)
         return r
 
     def _direction(self, who, direction):
