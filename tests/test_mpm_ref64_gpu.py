@@ -18,7 +18,7 @@ import pytest
 
 import ref64
 from util import rng, make_cloud, make_mixed_cloud, make_edge_cloud, make_drifting_cloud, make_uneven_cloud, make_full_cell_cloud, \
-    move_after_binning, tag_masses, OracleMpm, oracle_stress
+    move_after_binning, tag_masses, OracleMpm, oracle_stress, stress_tol as _stress_tol
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -83,15 +83,6 @@ def _fields(a, mt):
 def _by_mass(f):
     o = np.argsort(f["m"], kind="stable")
     return {k: v[o] for k, v in f.items()}
-
-
-def _stress_tol(om, PF, F):
-    """e_in of an oracle stress used in place of the kernel's: 1e-4 of the row scale (test_svd_and_stress_blocks)"""
-    mu, lam = C.c_float(), C.c_float()
-    om.o.orc_lame(C.c_float(om.p.E), C.c_float(om.p.nu), C.byref(mu), C.byref(lam))
-    scale = (2 * mu.value + lam.value) * om.p.volume
-    rowmag = np.maximum(np.abs(PF).max(1, keepdims=True), scale * np.maximum(1.0, np.abs(F - np.eye(3).reshape(1, 9)).max(1, keepdims=True)))
-    return np.broadcast_to(1e-4 * rowmag, PF.shape)
 
 
 def _grid_update_checked(mt, path, dt):

@@ -219,6 +219,99 @@ def oracle_stress(oracle, om, Cm, F, logJp=None):
     return out
 
 
+def stress_tol(om, PF, F):
+    """e_in of a stress computed by another instantiation than the one under test (the oracle's, the test entry's) used in place of
+    the kernel's own: 1e-4 of the row scale (test_svd_and_stress_blocks)"""
+    mu, lam = C.c_float(), C.c_float()
+    om.o.orc_lame(C.c_float(om.p.E), C.c_float(om.p.nu), C.byref(mu), C.byref(lam))
+    scale = (2 * mu.value + lam.value) * om.p.volume
+    rowmag = np.maximum(np.abs(PF).max(1, keepdims=True), scale * np.maximum(1.0, np.abs(F - np.eye(3).reshape(1, 9)).max(1, keepdims=True)))
+    return np.broadcast_to(1e-4 * rowmag, PF.shape)
+
+
+# ---------------------------------------------------------------------------------------- scenes of the gather-style (C2) ref64 tests
+C2_SCENES = ["lattice", "mixed", "edge", "edge_origin", "far", "faces", "counts", "lone"]
+_C2_CACHE = {}
+
+
+def _c2_fill(pos, seed, vel_scale=0.3):
+    g = rng(seed)
+    n = pos.shape[0]
+    vel = (vel_scale * g.standard_normal((n, 3))).astype(np.float32)
+    Cm = (0.1 * g.standard_normal((n, 9))).astype(np.float32)
+    F = (np.eye(3).reshape(1, 9) + 0.01 * g.standard_normal((n, 9))).astype(np.float32)
+    return vel, Cm, F
+
+
+def c2_scene(name, dx=1.0 / 64):
+    """Scenes of tests/test_c2_ref64_cpu.py and tests/test_c2_ref64_gpu.py: dict of mass, pos, vel, B (= C dx^2 / 4, the scale of
+    test_c2_gpu._setup), F, J (the fluid's state), logJp, key_is_origin and, for `lone`, block (the single block of its partition, in
+    block coordinates: the partition is adopted, not built).  dx must be a power of two.
+      lattice      make_cloud(7, dx, 2)
+      mixed        make_mixed_cloud(6, dx): three mass slabs m, 1e-3 m, 1e-6 m, momentum cancelling at the nodes
+      edge         make_edge_cloud(dx): straddles 0 on all axes (edge_origin: the same with block-origin keys)
+      far          lattice translated by (16, -16, 8): |x| / dx is 50 times larger
+      faces        cells 3 and 4 per axis (two blocks at side 4); per axis the in-cell fractions 0, 0+, 0.25, 0.5-, 0.5, 0.5+, 0.75, 1-
+                   (+ / -: the neighbouring float32), the third of the 512 combinations with (i + 2 j + 3 k) % 3 == 0: 176 per cell
+      counts       5^3 cells of 8 particles; five of them hold instead 21, 22, 255 (all in octant 0), 255 (all in octant 7) and 256
+      lone         one particle in the corner cell (side - 1, 0, 2) of a block that is the whole partition"""
+    if (name, dx) in _C2_CACHE:
+        return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in _C2_CACHE[(name, dx)].items()}
+    f = np.float32
+    block = None
+    if name in ("lattice", "far"):
+        mass, pos, vel, Cm, F = make_cloud(7, dx, 2, seed=71, vel_scale=0.3)
+        if name == "far":
+            pos = (pos + np.array([16.0, -16.0, 8.0], f)).astype(f)
+    elif name == "mixed":
+        mass, pos, vel, Cm, F = make_mixed_cloud(6, dx)
+    elif name in ("edge", "edge_origin"):
+        mass, pos, vel, Cm, F = make_edge_cloud(dx)
+    elif name == "faces":
+        fr = lambda c: [f(c), np.nextafter(f(c), f(99)), f(c + 0.25), np.nextafter(f(c + 0.5), f(-99)), f(c + 0.5),
+                        np.nextafter(f(c + 0.5), f(99)), f(c + 0.75), np.nextafter(f(c + 1), f(-99))]
+        ax = np.array(fr(3) + fr(4), f)                                   # [16] X = x / dx along one axis
+        i = np.stack(np.meshgrid(np.arange(16), np.arange(16), np.arange(16), indexing="ij"), -1).reshape(-1, 3)
+        i = i[((i % 8) @ np.array([1, 2, 3])) % 3 == 0]
+        pos = (ax[i] * f(dx)).astype(f)
+        vel, Cm, F = _c2_fill(pos, 72)
+        mass = np.full(len(pos), 1000.0 * dx ** 3 / 8, f)
+    elif name == "counts":
+        g = rng(73)
+        org = np.array([20, 20, 16])
+        mass, pos, _, _, _ = make_cloud(5, dx, 2, origin=tuple(org * dx), seed=74)
+        special = {(1, 1, 1): (21, 0.0, 1.0), (3, 1, 1): (22, 0.0, 1.0), (1, 3, 1): (255, 0.0, 0.5), (3, 3, 1): (255, 0.5, 0.5),
+                   (2, 2, 3): (256, 0.0, 1.0)}
+        cell = np.floor(pos.astype(np.float64) / dx).astype(int) - org
+        keep = np.ones(len(pos), bool)
+        extra = []
+        for c, (k, lo, width) in special.items():
+            keep &= ~(cell == np.array(c)).all(1)
+            extra.append(((org + np.array(c) + lo + width * (0.001 + 0.998 * g.random((k, 3)))) * dx).astype(f))
+        pos = np.concatenate([pos[keep]] + extra).astype(f)
+        vel, Cm, F = _c2_fill(pos, 75)
+        mass = np.full(len(pos), mass[0], f)
+    elif name == "lone":
+        block = (5, 5, 4)
+        pos = None   # depends on the block side: see c2_lone_pos
+        mass = np.full(1, 1000.0 * dx ** 3 / 8, f)
+        vel, Cm, F = _c2_fill(np.zeros((1, 3), f), 76)
+    else:
+        raise ValueError(name)
+    n = len(mass)
+    out = dict(mass=mass, pos=pos, vel=vel, B=(Cm * dx * dx * 0.25).astype(f), F=F,
+               J=(1.0 + 0.01 * rng(77).standard_normal((n, 1))).astype(f), logJp=(0.01 * rng(78).standard_normal(n)).astype(f),
+               key_is_origin=name == "edge_origin", block=block)
+    _C2_CACHE[(name, dx)] = out
+    return c2_scene(name, dx)
+
+
+def c2_lone_pos(block, side, dx=1.0 / 64):
+    """the lone particle: cell (side - 1, 0, 2) of the block, at fractions (0.7, 0.2, 0.4): of the 8 cells within dx, those one further
+    along x and one back along y are outside the partition"""
+    return ((np.array(block) * side + np.array([side - 1 + 0.7, 0.2, 2.4])) * dx).astype(np.float32).reshape(1, 3)
+
+
 def lbvh_boxes(n, seed, dup=False):
     """n AABBs [n][6] = {min xyz, max xyz}: jittered centres in the unit cube, extents 0.5-3 % (dup: centres snapped to a
     coarse lattice so that many morton codes coincide)."""
