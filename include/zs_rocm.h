@@ -929,6 +929,38 @@ ZS_ROCM_EXPORT int zs_rocm_mesh_friction_hessian_product(zs_rocm_policy *, const
                                                          const int *ptPairs, size_t npt, const int *eePairs, size_t nee, const float *record,
                                                          float mu, float epsv, const int *starts, const int *entries, float *scratch,
                                                          float *hx, int *status);
+/* ---- mesh elasticity (zpc_amd/csrc/mesh_elastic.hip, include/zensim_rocm/elastic_device.hpp): the internal energy of the mesh itself, StVK
+ * membrane energy over the triangles (mu, lam: per-area Lame stiffnesses, the thickness multiplied in) plus quadratic bending energy over
+ * the hinges (kb), against a rest shape kept in the mesh object; energy, gradient and matrix-free Hessian-vector product in the shape of
+ * the contact terms.  The bending energy is zero at rest only where the rest shape is flat across the hinge (cloth); on a curved rest
+ * shape it penalises the rest curvature too.
+ *   set_rest_shape  from verts [nv][3] or (NULL) the mesh's current vertices: the triangle records [nt][4] (B00, B01, B11, A), the hinges
+ *                   [nh][4] (every unique edge with exactly two triangles, in edge order: the edge's vertices v0 < v1, the opposite vertex of
+ *                   the incident triangle with the smaller index, that of the other), their records [nh][4] and the vertex areas [nv] (a
+ *                   third of the incident rest areas).  Degenerate rest triangles and hinges get all-zero records and contribute nothing.
+ *                   A second call recomputes the records and keeps the hinges.
+ *   sizes           sizes[0..3] = nt, nh, nv, floats of scratch (9 nt + 12 nh); sizes[4..6] = degenerate triangles, degenerate hinges,
+ *                   non-manifold edges (more than two triangles: no hinge) of the last set_rest_shape.  size_t sizes[7].
+ *   rest_shape      copies out triRecord [nt][4], hinges [nh][4], hingeRecord [nh][4], vertexArea [nv]; each may be NULL.
+ *   energy          triEnergy [nt], hingeEnergy [nh] (float), total (one double, triangles then hinges, summed in a fixed order), status
+ *                   int[2] = the triangles and hinges whose result leaves the float range (they contribute exactly zero).  Every output
+ *                   may be NULL.  verts NULL: the mesh's own positions.
+ *   gradient        the same and grad [nv][3], fully overwritten; scratch holds the per-element terms, [nt][3][3] then [nh][4][3].
+ *   product         hx [nv][3] = H x for the direction x [nv][3]; psd != 0: the positive semi-definite H+ (the membrane stress projected
+ *                   onto the positive semi-definite matrices in closed form), a majorant of H that equals it where no triangle is compressed.
+ * mu = lam = 0 skips the membrane, kb = 0 the bending; both then contribute exactly zero.  Two calls give the same bytes (no float
+ * atomics).  -1 and nothing written for a NULL policy, mesh, x, hx, grad (with vertices) or scratch (with elements), a stiffness that is
+ * negative or not finite, or before set_rest_shape. */
+ZS_ROCM_EXPORT int zs_rocm_mesh_set_rest_shape(zs_rocm_policy *, zs_rocm_mesh *, const float *verts);
+ZS_ROCM_EXPORT int zs_rocm_mesh_rest_shape_sizes(const zs_rocm_mesh *, size_t *sizes);
+ZS_ROCM_EXPORT int zs_rocm_mesh_rest_shape(zs_rocm_policy *, const zs_rocm_mesh *, float *triRecord, int *hinges, float *hingeRecord,
+                                           float *vertexArea);
+ZS_ROCM_EXPORT int zs_rocm_mesh_elastic_energy(zs_rocm_policy *, const zs_rocm_mesh *, const float *verts, float mu, float lam, float kb,
+                                               float *triEnergy, float *hingeEnergy, double *total, int *status);
+ZS_ROCM_EXPORT int zs_rocm_mesh_elastic_gradient(zs_rocm_policy *, const zs_rocm_mesh *, const float *verts, float mu, float lam, float kb,
+                                                 float *scratch, float *triEnergy, float *hingeEnergy, double *total, float *grad, int *status);
+ZS_ROCM_EXPORT int zs_rocm_mesh_elastic_hessian_product(zs_rocm_policy *, const zs_rocm_mesh *, const float *verts, float mu, float lam,
+                                                        float kb, int psd, const float *x, float *scratch, float *hx, int *status);
 /* ---- mesh CCD (zpc_amd/csrc/mesh_ccd.hip, include/zensim_rocm/ccd_device.hpp): a conservative bound on the step t in [0, tMax] for which
  * verts + t dir (verts NULL: the mesh's own positions; dir [nv][3]) keeps every pair of the two lists free of contact, by additive CCD on
  * the unsigned distance -- what a line search needs before it may evaluate the barrier.  The reference has yes / no tests only

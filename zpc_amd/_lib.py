@@ -484,7 +484,14 @@ def _declare_containers(L):
     L.zs_rocm_mesh_friction_energy.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, f32, f32, vp, vp, vp, vp]
     L.zs_rocm_mesh_friction_gradient.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.zs_rocm_mesh_friction_hessian_product.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, f32, f32, vp, vp, vp, vp, vp]
-    for name in ("friction_lag", "friction_energy", "friction_gradient", "friction_hessian_product"):
+    L.zs_rocm_mesh_set_rest_shape.argtypes = [vp, vp, vp]
+    L.zs_rocm_mesh_rest_shape_sizes.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.zs_rocm_mesh_rest_shape.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.zs_rocm_mesh_elastic_energy.argtypes = [vp, vp, vp, f32, f32, f32, vp, vp, vp, vp]
+    L.zs_rocm_mesh_elastic_gradient.argtypes = [vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp]
+    L.zs_rocm_mesh_elastic_hessian_product.argtypes = [vp, vp, vp, f32, f32, f32, i32, vp, vp, vp, vp]
+    for name in ("friction_lag", "friction_energy", "friction_gradient", "friction_hessian_product", "set_rest_shape", "rest_shape_sizes",
+                 "rest_shape", "elastic_energy", "elastic_gradient", "elastic_hessian_product"):
         getattr(L, "zs_rocm_mesh_" + name).restype = i32
     for name in ("refit", "total_box", "closest_point", "signed_distance", "levelset_candidates", "levelset_blocks", "levelset_gather", "edges",
                  "proximity_pt_count", "proximity_pt_fill", "proximity_ee_count", "proximity_ee_fill", "set_rest", "rest", "barrier_sizes",

@@ -39,7 +39,9 @@ EXTRA_FLAGS = {"mpm_slotted.hip": ["-fno-slp-vectorize"], "mpm_slotblk.hip": ["-
                # (friction_device.hpp) lags them, and its evaluation is replayed bit for bit in numpy
                "mesh_barrier.hip": ["-ffp-contract=off"],
                # additive CCD on those pairs (include/zensim_rocm/ccd_device.hpp) advances on the same distances
-               "mesh_ccd.hip": ["-ffp-contract=off"]}
+               "mesh_ccd.hip": ["-ffp-contract=off"],
+               # membrane and bending energy (include/zensim_rocm/elastic_device.hpp): replayed bit for bit in numpy
+               "mesh_elastic.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst):

@@ -549,6 +549,8 @@ void zs_rocm_mesh_destroy(zs_rocm_mesh *m) {
   (void)hipFree(m->edges); (void)hipFree(m->edgeBoxes); (void)hipFree(m->triPacked); (void)hipFree(m->edgePacked);
   (void)hipFree(m->ptCache); (void)hipFree(m->ptCacheCounts); (void)hipFree(m->eeCache); (void)hipFree(m->eeCacheCounts);
   (void)hipFree(m->restLen2);
+  (void)hipFree(m->hinges); (void)hipFree(m->hingeStarts); (void)hipFree(m->hingeEntries); (void)hipFree(m->cornerStarts);
+  (void)hipFree(m->triRecord); (void)hipFree(m->hingeRecord); (void)hipFree(m->vertArea);
   zs_rocm_lbvh_destroy(m->bvh);
   if (m->edgeBvh) zs_rocm_lbvh_destroy(m->edgeBvh);
   delete m;

@@ -1,6 +1,6 @@
 // mesh.hpp -- the triangle-mesh object of the C ABI, shared by mesh.hip (colliders, mesh -> level set), mesh_proximity.hip (the
 // point-triangle and edge-edge pairs within a contact distance), mesh_barrier.hip (the contact potential on those pairs) and mesh_ccd.hip
-// (the largest step along a direction that keeps those pairs apart).
+// (the largest step along a direction that keeps those pairs apart) and mesh_elastic.hip (the membrane and bending energy of the mesh itself).
 #pragma once
 #include "common.hpp"
 #include "../../include/zensim_rocm/mesh_device.hpp"
@@ -39,6 +39,15 @@ struct zs_rocm_mesh {
   // the squared rest length of every unique edge (mesh_barrier.hip: the threshold of the edge-edge mollifier), set by zs_rocm_mesh_set_rest
   float *restLen2 = nullptr;
   bool hasRest = false;
+  // the rest shape (mesh_elastic.hip), set by zs_rocm_mesh_set_rest_shape.  Topology only, built by the first call: the hinges [nh][4] (the
+  // unique edges with exactly two triangles, in edge order: edge, then the opposite vertices of the smaller and the other triangle), their
+  // incidence by vertex (entries 4 hinge + corner, hinge order inside a vertex; hingeStarts [nv + 1]) and the run starts of cornerKeys
+  // [nv + 1].  From the rest positions, recomputed by every call: the triangle records [nt][4], the hinge records [nh][4], the vertex areas [nv]
+  size_t nh = 0;
+  int *hinges = nullptr, *hingeStarts = nullptr, *hingeEntries = nullptr, *cornerStarts = nullptr;
+  float *triRecord = nullptr, *hingeRecord = nullptr, *vertArea = nullptr;
+  int restShapeCounts[3] = {0, 0, 0};  // degenerate triangles, degenerate hinges, non-manifold edges
+  bool hasHinges = false, hasRestShape = false;
   zsr::TriMeshDev dev() const {
     zsr::TriMeshDev d;
     d.verts = verts; d.tris = tris; d.vel = hasVel ? vel : nullptr;
@@ -86,6 +95,9 @@ __device__ __forceinline__ void pair_rows(const float *__restrict__ src, const i
 
 // 4 (npt + nee) incidence entries are ints and go through one radix sort call
 inline bool barrier_counts_ok(size_t npt, size_t nee) { return npt + nee < ((size_t)1 << 28); }
+
+// mesh_barrier.hip: the float64 total of the floats a [na] then b [nb], summed in a fixed order (its two reduction kernels)
+void barrier_launch_total(Launch &L, const float *a, size_t na, const float *b, size_t nb, double *total);
 
 // mesh_proximity.hip: after new vertex positions -- the packed nodes are stale, the edge tree (if built) is refitted; -1 on failure
 int mesh_proximity_refit(zs_rocm_policy *pol, zs_rocm_mesh &m);

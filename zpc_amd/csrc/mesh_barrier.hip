@@ -264,8 +264,8 @@ static void barrier_launch_pairs(Launch &L, const zs_rocm_mesh *m, const float *
   }
 }
 
-// the float64 total of the per-pair energies, PT then EE
-static void barrier_launch_total(Launch &L, const float *ptEnergy, size_t npt, const float *eeEnergy, size_t nee, double *total) {
+// the float64 total of the per-pair energies, PT then EE (mesh.hpp: mesh_elastic.hip sums its per-element energies with it)
+void barrier_launch_total(Launch &L, const float *ptEnergy, size_t npt, const float *eeEnergy, size_t nee, double *total) {
   const size_t n = npt + nee, parts = (n + RED_CHUNK - 1) / RED_CHUNK;
   double *partial = parts ? (double *)L.temp(sizeof(double) * parts) : nullptr;
   if (parts) hipLaunchKernelGGL(barrier_partial_kernel, dim3((unsigned)parts), dim3(BAR_BLOCK), 0, L.stream, ptEnergy, npt, eeEnergy, nee, partial);

@@ -1,7 +1,8 @@
 """Triangle meshes as colliders: TriMesh owns a device mesh object of the library (LBvh over the triangle boxes, face normals, vertex and
 edge pseudonormals) and answers closest-point and signed-distance queries and the proximity pairs of the mesh with itself (vertex-triangle and edge-edge within a
-contact distance), the IPC barrier potential with its gradient and Hessian-vector product on those pairs and the largest step along a
-direction that keeps them apart (max_step, step_candidates); SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
+contact distance), the IPC barrier potential with its gradient and Hessian-vector product on those pairs, the largest step along a
+direction that keeps them apart (max_step, step_candidates) and the mesh's own membrane and bending energy against a rest shape
+(set_rest_shape, elastic, elastic_hessian_product); SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
 into a sparse level set.  Set-up code: torch for the plumbing; every query runs in the library's HIP kernels."""
 import ctypes as C
 
@@ -131,6 +132,34 @@ class FrictionHessianProduct:
     """result of TriMesh.friction_hessian_product: hx [nv, 3] float32 = H x, pair_terms [npt + nee, 4, 3] float32 (the contributions
     (H_pair x) on each pair's four corners, PT pairs first: the scratch of the call), overflow as for Friction"""
     __slots__ = ("hx", "pair_terms", "overflow")
+
+
+class _ElementTerms:
+    """the scratch of an elastic call, elem_terms [9 nt + 12 nh] float32, as its two parts"""
+    __slots__ = ()
+
+    @property
+    def tri_terms(self):
+        return None if self.elem_terms is None else self.elem_terms[:9 * self.nt].view(self.nt, 3, 3)
+
+    @property
+    def hinge_terms(self):
+        return None if self.elem_terms is None else self.elem_terms[9 * self.nt:].view((self.elem_terms.numel() - 9 * self.nt) // 12, 4, 3)
+
+
+class Elastic(_ElementTerms):
+    """result of TriMesh.elastic: energy (float64 device scalar: triangles then hinges, summed in a fixed order), tri_energy [nt],
+    hinge_energy [nh], grad [nv, 3] or None, elem_terms (the scratch of a gradient call: the gradient terms on each triangle's three
+    corners, then on each hinge's four; tri_terms [nt, 3, 3] and hinge_terms [nh, 4, 3] are views of it; None without the gradient),
+    overflow = (triangles, hinges) whose energy or gradient leaves the float range (they contribute exactly zero)"""
+    __slots__ = ("energy", "tri_energy", "hinge_energy", "grad", "elem_terms", "overflow", "nt")
+
+
+class ElasticHessianProduct(_ElementTerms):
+    """result of TriMesh.elastic_hessian_product: hx [nv, 3] float32 = H x, elem_terms [9 nt + 12 nh] float32 (the scratch of the call: the
+    contributions (H_element x) on each triangle's three corners, then on each hinge's four; tri_terms [nt, 3, 3] and hinge_terms
+    [nh, 4, 3] are views of it), overflow as for Elastic"""
+    __slots__ = ("hx", "elem_terms", "overflow", "nt")
 
 
 class StepBound:
@@ -451,6 +480,102 @@ class TriMesh:
                                                        lag.record.data_ptr(), mu, eps_v, starts.data_ptr(), entries.data_ptr(),
                                                        r.pair_terms.data_ptr(), r.hx.data_ptr(), status.data_ptr()) != 0:
             raise RuntimeError("the friction Hessian product call failed")
+        r.overflow = self._zero_distance(status)
+        return r
+
+    def set_rest_shape(self, verts=None):
+        """stores the rest shape of the mesh's internal energy from verts [nv, 3], or from the mesh's current vertices: the membrane record
+        of every triangle, the hinges (unique edges with exactly two triangles) with their bending records and the vertex areas.  Returns
+        the counts (degenerate triangles, degenerate hinges, non-manifold edges): those elements contribute nothing (a non-manifold edge
+        makes no hinge).  A second call recomputes the records on the same hinges.  Leaves set_rest and the contact terms alone."""
+        v = None if verts is None else _dev_f32(verts, 3)
+        if v is not None and v.shape[0] != self.nv:
+            raise ValueError("TriMesh.set_rest_shape: [nv, 3] positions on the same topology")
+        if lib().zs_rocm_mesh_set_rest_shape(self.pol.handle, self._h, _ptr(v)) != 0:
+            raise RuntimeError("zs_rocm_mesh_set_rest_shape failed")
+        self.pol.syncCtx()
+        sizes = (C.c_size_t * 7)()
+        if lib().zs_rocm_mesh_rest_shape_sizes(self._h, sizes) != 0:
+            raise RuntimeError("zs_rocm_mesh_rest_shape_sizes failed")
+        self.num_hinges, self._elastic_scratch = int(sizes[1]), int(sizes[3])
+        self.has_rest_shape = True
+        return int(sizes[4]), int(sizes[5]), int(sizes[6])
+
+    def rest_shape(self):
+        """(tri_record [nt, 4] float32 (B00, B01, B11, A), hinges [nh, 4] int32, hinge_record [nh, 4] float32, vertex_area [nv] float32) on
+        the device.  A hinge row is (v0, v1, v2, v3): v0 < v1 the edge, as in a row of TriMesh.edges(), v2 opposite in the incident triangle
+        with the smaller index, v3 in the other; hinges are in edge order.  Lumped masses are density * vertex_area."""
+        import torch
+        if not getattr(self, "has_rest_shape", False):
+            raise ValueError("TriMesh.rest_shape: call set_rest_shape first")
+        f32, nh = dict(dtype=torch.float32, device="cuda"), self.num_hinges
+        rec, hinges = torch.empty(self.nt, 4, **f32), torch.empty(nh, 4, dtype=torch.int32, device="cuda")
+        hrec, area = torch.empty(nh, 4, **f32), torch.empty(self.nv, **f32)
+        if lib().zs_rocm_mesh_rest_shape(self.pol.handle, self._h, rec.data_ptr(), hinges.data_ptr(), hrec.data_ptr(), area.data_ptr()) != 0:
+            raise RuntimeError("zs_rocm_mesh_rest_shape failed")
+        self.pol.syncCtx()
+        return rec, hinges, hrec, area
+
+    def _elastic_args(self, who, mu, lam, kb, verts):
+        """what elastic and elastic_hessian_product (who, for the messages) share: the arguments checked; returns the trial positions or
+        None and the head of the C call up to kb"""
+        mu, lam, kb = float(mu), float(lam), float(kb)
+        for name, x in (("mu", mu), ("lam", lam), ("kb", kb)):
+            if not (0 <= x <= FLT_MAX):
+                raise ValueError("TriMesh.%s: %s must be finite and not negative" % (who, name))
+        if not getattr(self, "has_rest_shape", False):
+            raise ValueError("TriMesh.%s: needs the rest shape, call set_rest_shape first" % who)
+        v = None if verts is None else _dev_f32(verts, 3)
+        if v is not None and v.shape[0] != self.nv:
+            raise ValueError("TriMesh.%s: verts are [nv, 3] positions on the same topology" % who)
+        return v, (self.pol.handle, self._h, _ptr(v), mu, lam, kb)
+
+    def elastic(self, mu, lam, kb, verts=None, gradient=True):
+        """the internal energy of the mesh against the rest shape of set_rest_shape, and its gradient: an Elastic.  Membrane: St.
+        Venant-Kirchhoff, A (mu |E|^2 + lam / 2 tr(E)^2) per triangle, E the Green strain of the 3 x 2 deformation gradient, mu and lam
+        per-area stiffnesses (the thickness multiplied in).  Bending: the quadratic (isometric) energy of Bergou et al. 2006, kb / 2 |sum_i
+        k_i x_i|^2 per hinge.  Its domain is cloth: it is zero at rest only where the rest shape is flat across the hinge, and on a curved
+        rest shape it penalises the rest curvature too.  verts [nv, 3]: trial positions instead of the mesh's own.  A zero mu and lam (or
+        kb) skips the membrane (or bending) kernels.  Two calls give the same bytes."""
+        import torch
+        v, head = self._elastic_args("elastic", mu, lam, kb, verts)
+        f32 = dict(dtype=torch.float32, device="cuda")
+        r = Elastic()
+        r.energy = torch.empty((), dtype=torch.float64, device="cuda")
+        r.tri_energy, r.hinge_energy = torch.empty(self.nt, **f32), torch.empty(self.num_hinges, **f32)
+        r.grad, r.elem_terms, r.nt = None, None, self.nt
+        status = torch.empty(2, dtype=torch.int32, device="cuda")
+        tail = (r.tri_energy.data_ptr(), r.hinge_energy.data_ptr(), r.energy.data_ptr())
+        if gradient:
+            r.elem_terms = torch.empty(self._elastic_scratch, **f32)
+            r.grad = torch.empty(self.nv, 3, **f32)
+            rc = lib().zs_rocm_mesh_elastic_gradient(*head, r.elem_terms.data_ptr(), *tail, r.grad.data_ptr(), status.data_ptr())
+        else:
+            rc = lib().zs_rocm_mesh_elastic_energy(*head, *tail, status.data_ptr())
+        if rc != 0:
+            raise RuntimeError("the elastic call failed")
+        r.overflow = self._zero_distance(status)
+        return r
+
+    def elastic_hessian_product(self, mu, lam, kb, x, verts=None, psd=False):
+        """H x for a direction x [nv, 3], H the second derivative of the energy of TriMesh.elastic, matrix-free: an ElasticHessianProduct.
+        psd: the positive semi-definite H+, the membrane stress replaced by its closed-form projection onto the positive semi-definite
+        matrices where it multiplies the direction's deformation gradient; H+ majorises H and equals it wherever no triangle is
+        compressed, and is the operator a conjugate-gradient solve can use.  The bending part is positive semi-definite as it stands.  Two
+        calls give the same bytes."""
+        import torch
+        v, head = self._elastic_args("elastic_hessian_product", mu, lam, kb, verts)
+        d = _dev_f32(x, 3)
+        if d.shape[0] != self.nv:
+            raise ValueError("TriMesh.elastic_hessian_product: x is an [nv, 3] direction")
+        r = ElasticHessianProduct()
+        r.nt = self.nt
+        r.elem_terms = torch.empty(self._elastic_scratch, dtype=torch.float32, device="cuda")
+        r.hx = torch.empty(self.nv, 3, dtype=torch.float32, device="cuda")
+        status = torch.empty(2, dtype=torch.int32, device="cuda")
+        if lib().zs_rocm_mesh_elastic_hessian_product(*head, 1 if psd else 0, d.data_ptr(), r.elem_terms.data_ptr(), r.hx.data_ptr(),
+                                                      status.data_ptr()) != 0:
+            raise RuntimeError("the elastic Hessian product call failed")
         r.overflow = self._zero_distance(status)
         return r
 
