@@ -889,8 +889,8 @@ ZS_ROCM_EXPORT int zs_rocm_mesh_barrier_gradient(zs_rocm_policy *, const zs_rocm
 /* The Hessian-vector product of the same potential over the same lists, matrix-free (the job of barrier_hessian with dist_hess_pp / _pe /
  * _pt / _ee, geometry/Distance.hpp, as an operator): hx [nv][3] = H x for a direction x [nv][3], H the second derivative of the total
  * energy at verts (NULL: the mesh's own).  Per pair (H_pair x) on its four corners goes to scratch (sizes[2] floats, PT pairs first, [4][3]
- * each; the caller may read them), then barrier_gather sums them per vertex in list order on starts / entries of _barrier_incidence: no
- * float atomics, two calls give the same bytes.  psd != 0: the positive semi-definite H+ of barrier_device.hpp (b'' g g^T + |b'| F^T A^-1 F,
+ * each; the caller may read them), then the gather of mesh_terms.hip sums them per vertex in list order on starts / entries of
+ * _barrier_incidence: no float atomics, two calls give the same bytes.  psd != 0: the positive semi-definite H+ of barrier_device.hpp (b'' g g^T + |b'| F^T A^-1 F,
  * mollified: m H+_b + b m' 2 J^T J), a majorant of H without the mollifier; it is not the eigenvalue projection of the 12 x 12 blocks.
  * status as above; a pair at zero distance (or whose b'' or product leaves the float range) contributes zero and is counted.  -1 for the
  * argument errors of _barrier_gradient, or x or hx NULL with nv > 0. */

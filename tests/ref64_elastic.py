@@ -47,6 +47,7 @@ import numpy as np
 
 import ref64_proximity as rp
 from ref64_mesh import U, _cross, _dot
+from ref64_terms import incidence, gather, total      # the gather and the total, in the device's order
 
 K_REC, K_HINGE = 40.0, 48.0
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -280,48 +281,6 @@ def hinge_bounds(X, x, kb, z=None):
     idle = st != ACTIVE
     zero = lambda b: None if b is None else np.where(idle.reshape((-1,) + (1,) * (b.ndim - 1)), 0.0, b)
     return zero(be), zero(bg), zero(bh)
-
-
-# ------------------------------------------------------------------------------------------------ gather and total, in the device's order
-def incidence(elems, nv):
-    """(starts [nv + 1], entries): the numbers N element + corner of the corners of elems [n, N] stably sorted by vertex"""
-    flat = np.asarray(elems, np.int64).reshape(-1)
-    order = np.argsort(flat, kind="stable")
-    return np.searchsorted(flat[order], np.arange(nv + 1)), order
-
-
-def gather(nv, runs, dtype):
-    """out [nv, ...]: for every vertex the sum of terms[entries] over its runs, one run after the other, each front to back, added one at
-    a time in dtype.  runs: a list of (starts, entries, terms [n * N, ...])"""
-    out = None
-    for starts, entries, terms in runs:
-        terms = np.asarray(terms, dtype)
-        if out is None:
-            out = np.zeros((nv,) + terms.shape[1:], dtype)
-        deg = np.diff(starts)
-        for k in range(int(deg.max()) if len(deg) else 0):
-            v = np.nonzero(deg > k)[0]
-            out[v] = out[v] + terms[entries[starts[v] + k]]
-    return out
-
-
-def total(energies):
-    """the float64 sum of float32 energies in the order of barrier_partial_kernel / barrier_total_kernel: workgroup g takes elements
-    [4096 g, 4096 (g + 1)), thread t of 256 the elements t, t + 256, ..; then an LDS tree; one workgroup sums the partials the same way"""
-    def block(a, chunk):
-        pad = np.zeros(chunk, np.float64)
-        pad[:len(a)] = a
-        s = np.zeros(256)
-        for row in pad.reshape(-1, 256):
-            s = s + row
-        h = 128
-        while h:
-            s[:h] = s[:h] + s[h:2 * h]
-            h //= 2
-        return s[0]
-    a = np.asarray(energies, np.float32).astype(np.float64)
-    parts = np.array([block(a[i:i + 4096], 4096) for i in range(0, len(a), 4096)])
-    return block(parts, 256 * max(1, -(-len(parts) // 256)))
 
 
 # ------------------------------------------------------------------------------------------------ a scene

@@ -59,6 +59,7 @@ import numpy as np
 import ref64_barrier as rb
 import ref64_mesh as rm
 import ref64_proximity as rp
+import ref64_terms as rt
 from ref64_mesh import U, _dot, _cross
 
 FLT_MAX, FLT_MIN = rb.FLT_MAX, rb.FLT_MIN
@@ -483,16 +484,6 @@ def evaluate32(rec, urows, mu, eps, xrows=None):
 
 
 def gather32(terms, vert, nv):
-    """barrier_gather_kernel: per vertex the float32 sum of its (pair, corner) terms [n, 4, 3] front to back in list order; vert [n, 4], -1
+    """per vertex the float32 sum of its (pair, corner) terms [n, 4, 3] front to back in list order (ref64_terms.gather); vert [n, 4], -1
     for a corner that is not in the mesh"""
-    f = np.float32
-    flat, idx = _f32(terms).reshape(-1, 3), np.asarray(vert, np.int64).ravel()
-    keep = np.flatnonzero(idx >= 0)
-    order = keep[np.argsort(idx[keep], kind="stable")]
-    counts = np.bincount(idx[keep], minlength=nv)
-    starts = np.concatenate([[0], np.cumsum(counts)])
-    out = np.zeros((nv, 3), f)
-    for j in range(int(counts.max()) if len(counts) else 0):
-        sel = np.flatnonzero(counts > j)
-        out[sel] = out[sel] + flat[order[starts[sel] + j]]
-    return out
+    return rt.gather(nv, [rt.incidence(vert, nv) + (_f32(terms).reshape(-1, 3),)], np.float32)

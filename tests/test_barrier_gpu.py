@@ -14,6 +14,7 @@ import pytest
 
 import ref64_barrier as rb
 import ref64_proximity as rp
+import ref64_terms as rt
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -39,6 +40,12 @@ def _np(x):
     return None if x is None else x.cpu().numpy()
 
 
+def _total_is_the_replay(B):
+    """the float64 total of a Barrier is the reduction of tests/ref64_terms.py over its float32 energies, PT then EE, bit for bit"""
+    own = [a for a in (_np(B.pt_energy), _np(B.ee_energy)) if a is not None]
+    assert _np(B.energy).tobytes() == np.float64(rt.total(np.concatenate(own))).tobytes()
+
+
 def _compare(what, B, R, nv):
     """the checks of one Barrier against one Reference; returns the per-vertex ratio"""
     pe, ee, g = _np(B.pt_energy), _np(B.ee_energy), _np(B.grad)
@@ -57,6 +64,7 @@ def _compare(what, B, R, nv):
     assert np.isinf(tb) or abs(total - R.energy) <= tb, (what, total, R.energy, tb)
     own = float(pe.astype(np.float64).sum() + ee.astype(np.float64).sum())      # the total is the sum of the energies it returns
     assert total == own or abs(total - own) <= 1e-13 * own
+    _total_is_the_replay(B)
     assert g.shape == (nv, 3) and g.dtype == np.float32 and np.isfinite(g).all()
     err = np.linalg.norm(g.astype(np.float64) - R.grad, axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -89,6 +97,8 @@ def test_energy_and_gradient_against_the_float64_reference(pol, name, mollify):
         assert R.ninc.max() > 64
     if name == "stack":
         assert np.sort(R.ninc)[len(R.ninc) // 2] > 64
+        # the total's two arrays meet inside a chunk of 4096, off a multiple of 256
+        assert len(B.pt_energy) + len(B.ee_energy) > 4096 and len(B.pt_energy) % 256 != 0 and len(B.pt_energy) % 4096 != 0
     if name in ("sheets", "regular", "torus", "fan", "stack"):
         assert float(B.energy.item()) > 0 and np.abs(_np(B.grad)).max() > 0
     if name == "sheets" and mollify:
@@ -262,7 +272,8 @@ def test_arguments(pol):
     full = mesh.barrier(prox, dhat, KAPPA)
     only_pt, only_ee = mesh.proximity(dhat, ee=False), mesh.proximity(dhat, pt=False)
     P, E = mesh.barrier(only_pt, dhat, KAPPA), mesh.barrier(only_ee, dhat, KAPPA)
-    assert P.ee_energy is None and E.pt_energy is None
+    assert P.ee_energy is None and E.pt_energy is None and len(P.pt_energy) > 0 and len(E.ee_energy) > 0
+    _total_is_the_replay(P), _total_is_the_replay(E)
     assert _np(P.pt_energy).tobytes() == _np(full.pt_energy).tobytes() and _np(E.ee_energy).tobytes() == _np(full.ee_energy).tobytes()
     both = float(P.energy.item()) + float(E.energy.item())
     assert abs(both - float(full.energy.item())) <= 1e-14 * both and both > 0

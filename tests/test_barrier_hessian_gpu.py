@@ -16,6 +16,7 @@ import pytest
 import ref64_barrier as rb
 import ref64_barrier_hessian as rh
 import ref64_proximity as rp
+import ref64_terms as rt
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -105,12 +106,8 @@ def test_the_product_is_the_front_to_back_float32_sum_of_the_pair_terms(pol, nam
     prox = mesh.proximity(dhat)
     P = mesh.barrier_hessian_product(prox, dhat, KAPPA, rh.direction(mesh.nv, 1))
     starts, entries = (_np(z).astype(np.int64) for z in prox._incidence[:2])
-    terms = _np(P.pair_terms).reshape(-1, 3)
     run = np.diff(starts)
-    s = np.zeros((mesh.nv, 3), np.float32)
-    for j in range(int(run.max())):
-        live = np.where(run > j)[0]
-        s[live] = s[live] + terms[entries[starts[live] + j]]
+    s = rt.gather(mesh.nv, [(starts, entries, _np(P.pair_terms).reshape(-1, 3))], np.float32)
     print("HESSIAN gather[%s]: %d vertices, longest run %d" % (name, mesh.nv, run.max()))
     assert starts[-1] == 4 * len(P.pair_terms) and run.max() > (64 if name == "fan" else 1)
     assert _bytes(P.hx) == s.tobytes()

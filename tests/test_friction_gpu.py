@@ -18,6 +18,7 @@ import pytest
 import ref64_barrier as rb
 import ref64_friction as rf
 import ref64_proximity as rp
+import ref64_terms as rt
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -201,6 +202,7 @@ def _check_evaluation(what, pol, mesh, lag, t, e, u, x, mu=MU):
     assert np.array_equal(_bits(_np(F.grad)), _bits(rf.gather32(ev["g"], vert, nv))), what
     total, own = float(F.energy.item()), float(got(F).astype(np.float64).sum())      # the total is the sum of the energies it returns
     assert (total == own or abs(total - own) <= 1e-13 * own) and _np(E.energy).tobytes() == _np(F.energy).tobytes()
+    assert _np(F.energy).tobytes() == np.float64(rt.total(got(F))).tobytes(), what      # the reduction of ref64_terms, bit for bit
     return F, H
 
 
@@ -227,6 +229,10 @@ def test_energy_gradient_and_product_from_the_devices_own_record(pol, name):
             assert float(F.energy.item()) > 0 and np.abs(g).max() > 0 and np.abs(hx).max() > 0
     if name in ("fan", "stack"):      # runs longer than a wave
         assert ninc.max() > 64
+    if name == "stack":      # the total's two arrays meet inside a chunk of 4096, off a multiple of 256
+        assert len(pt) + len(ee) > 4096 and len(pt) % 256 != 0 and len(pt) % 4096 != 0
+    if name == "tiny0":
+        assert len(pt) + len(ee) == 0
 
 
 def test_a_displacement_beyond_the_float_range_is_counted_and_adds_nothing(pol):
@@ -302,7 +308,7 @@ def test_a_side_that_is_none_and_mu_zero(pol):
     npt = len(only_pt.pt_pairs)
     assert _np(Lp.record).tobytes() == _np(full.record)[:npt].tobytes() and _np(Le.record).tobytes() == _np(full.record)[npt:].tobytes()
     P, E = mesh.friction(Lp, u, MU, EPS), mesh.friction(Le, u, MU, EPS)
-    assert P.ee_energy is None and E.pt_energy is None
+    assert P.ee_energy is None and E.pt_energy is None and len(P.pt_energy) > 0 and len(E.ee_energy) > 0      # the totals: _check_evaluation
     assert _np(P.pt_energy).tobytes() == _np(Ff.pt_energy).tobytes() and _np(E.ee_energy).tobytes() == _np(Ff.ee_energy).tobytes()
     both = float(P.energy.item()) + float(E.energy.item())
     assert abs(both - float(Ff.energy.item())) <= 1e-14 * both and both > 0

@@ -400,12 +400,6 @@ __global__ __launch_bounds__(256) void mesh_ls_gather_kernel(const int *keys, co
   for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) dst[(size_t)bno * n + i] = src[blk * (size_t)n + i];
 }
 
-static int bits_for(size_t n) {
-  int b = 1;
-  while (b < 32 && ((size_t)1 << b) < n) ++b;
-  return b;
-}
-
 // face normals, boxes and angles from the current vertices
 static void mesh_faces(Launch &L, zs_rocm_mesh &m) {
   ZSR_CHECK(hipMemsetAsync(m.stats, 0, sizeof(int) * 4, L.stream));  // [4] (indices out of range) is a property of the topology
@@ -531,7 +525,7 @@ zs_rocm_mesh *zs_rocm_mesh_create(zs_rocm_policy *pol, const float *verts, size_
       unsigned *ck = (unsigned *)L.temp(sizeof(unsigned) * n3);
       int *ids = (int *)L.temp(sizeof(int) * n3);
       hipLaunchKernelGGL(mesh_keys_kernel, dim3(ceil_div(n3, 256)), dim3(256), 0, L.stream, m->tris, n3, hk, ck, ids);
-      const int vb = bits_for(nv);
+      const int vb = key_bits(nv);
       radix_sort_pair_u64(L, hk, ids, m->heKeys, m->heVals, n3, 0, 32 + vb);
       radix_sort_pair_u32(L, ck, ids, m->cornerKeys, m->cornerVals, n3, 0, vb);
       mesh_edges(L, *m);

@@ -1,6 +1,7 @@
 // mesh.hpp -- the triangle-mesh object of the C ABI, shared by mesh.hip (colliders, mesh -> level set), mesh_proximity.hip (the
-// point-triangle and edge-edge pairs within a contact distance), mesh_barrier.hip (the contact potential on those pairs) and mesh_ccd.hip
-// (the largest step along a direction that keeps those pairs apart) and mesh_elastic.hip (the membrane and bending energy of the mesh itself).
+// point-triangle and edge-edge pairs within a contact distance), mesh_barrier.hip (the contact potential on those pairs), mesh_ccd.hip
+// (the largest step along a direction that keeps those pairs apart), mesh_elastic.hip (the membrane and bending energy of the mesh itself)
+// and mesh_terms.hip (incidence, gather and total behind the barrier, friction and elastic terms).
 #pragma once
 #include "common.hpp"
 #include "../../include/zensim_rocm/mesh_device.hpp"
@@ -86,9 +87,10 @@ __device__ __forceinline__ bool pair_corners(const int *pairs, const int *prims,
 }
 
 // rows idx of an [nv][3] array
-__device__ __forceinline__ void pair_rows(const float *__restrict__ src, const int (&idx)[4], float (&out)[4][3]) {
+template <int N>
+__device__ __forceinline__ void vertex_rows(const float *__restrict__ src, const int (&idx)[N], float (&out)[N][3]) {
 #pragma unroll
-  for (int k = 0; k < 4; ++k)
+  for (int k = 0; k < N; ++k)
 #pragma unroll
     for (int d = 0; d < 3; ++d) out[k][d] = src[3 * (size_t)idx[k] + d];
 }
@@ -96,8 +98,59 @@ __device__ __forceinline__ void pair_rows(const float *__restrict__ src, const i
 // 4 (npt + nee) incidence entries are ints and go through one radix sort call
 inline bool barrier_counts_ok(size_t npt, size_t nee) { return npt + nee < ((size_t)1 << 28); }
 
-// mesh_barrier.hip: the float64 total of the floats a [na] then b [nb], summed in a fixed order (its two reduction kernels)
-void barrier_launch_total(Launch &L, const float *a, size_t na, const float *b, size_t nb, double *total);
+// the bits a radix sort has to look at for the keys 0 .. count - 1 (at least one)
+inline int key_bits(size_t count) {
+  int b = 1;
+  while (b < 32 && ((size_t)1 << b) < count) ++b;
+  return b;
+}
+
+// ---- mesh_terms.hip: what barrier, friction and elasticity share behind their per-element kernels, which write one float32 energy per
+// element and its [corners][3] terms to a scratch array: the incidence by vertex, the gather in run order, the float64 total
+constexpr int TERM_BLOCK = 256;
+
+// the incidence of n entries (entry c = corners * element + corner).  IncidenceKeys: the temporaries of one build, the sort key and number
+// of every entry and the per-vertex counts (zeroed by incidence_begin), filled through incidence_emit; incidence_end sorts the entries
+// stably by key into entries [n], so a vertex's run is in entry order, and scans the counts into starts [nv + 1]
+struct IncidenceKeys {
+  unsigned *keys;
+  int *vals;
+  unsigned *counts;
+};
+IncidenceKeys incidence_begin(Launch &L, size_t n, size_t nv);
+void incidence_end(Launch &L, const IncidenceKeys &k, size_t n, size_t nv, int *starts, int *entries);
+
+// entry c belongs to vertex v; an index outside the mesh gets the key nv: sorted behind every vertex and never read
+__device__ __forceinline__ void incidence_emit(const IncidenceKeys &k, size_t c, int v, int nv) {
+  const bool ok = (unsigned)v < (unsigned)nv;
+  k.keys[c] = ok ? (unsigned)v : (unsigned)nv;
+  k.vals[c] = (int)c;
+  if (ok) atomicAdd(k.counts + v, 1u);
+}
+// lane = entry; vertexOf(c) is the vertex of entry c, any value outside [0, nv) where it has none
+template <class VertexOf>
+__global__ __launch_bounds__(TERM_BLOCK) void incidence_kernel(const VertexOf vertexOf, size_t n, int nv, const IncidenceKeys k) {
+  const size_t c = (size_t)blockIdx.x * TERM_BLOCK + threadIdx.x;
+  if (c < n) incidence_emit(k, c, vertexOf(c), nv);
+}
+template <class VertexOf>
+void incidence_build(Launch &L, const VertexOf &vertexOf, size_t n, size_t nv, int *starts, int *entries) {
+  const IncidenceKeys k = incidence_begin(L, n, nv);
+  if (n) hipLaunchKernelGGL(incidence_kernel<VertexOf>, dim3(ceil_div(n, TERM_BLOCK)), dim3(TERM_BLOCK), 0, L.stream, vertexOf, n, (int)nv, k);
+  incidence_end(L, k, n, nv, starts, entries);
+}
+
+// one run per vertex: entries [starts[v], starts[v + 1]) index rows of terms [..][3]
+struct TermRun {
+  const int *starts, *entries;
+  const float *terms;
+};
+// out [nv][3]: lane = vertex sums the rows of its nruns (1 or 2) runs, one run after the other, each front to back
+void terms_gather(Launch &L, const TermRun *runs, int nruns, size_t nv, float *out);
+// the float64 total of the floats a [na] then b [nb], summed in a fixed order
+void terms_total(Launch &L, const float *a, size_t na, const float *b, size_t nb, double *total);
+// the caller's two status counts or a temporary, zeroed
+int *terms_status(Launch &L, int *status);
 
 // mesh_proximity.hip: after new vertex positions -- the packed nodes are stale, the edge tree (if built) is refitted; -1 on failure
 int mesh_proximity_refit(zs_rocm_policy *pol, zs_rocm_mesh &m);

@@ -12,13 +12,9 @@
 //             and writes one 32-byte record (n, lambda, w) per pair, PT pairs first; friction energy, gradient and product gather the
 //             displacement u where the barrier gathers positions, read the record and never touch the distance code.  Their per-pair
 //             energies and [4][3] contributions go through the same sum and the same gather.
-//   energy    float64 sum of the per-pair energies, PT then EE, in a fixed order: workgroup g sums elements [g, g + 1) x RED_CHUNK, thread
-//             t the elements t, t + 256, .. of the chunk, then an LDS tree; one workgroup sums the partials the same way.
-//   incidence built once per pair of lists, independent of the positions: the 4 (npt + nee) (vertex, 4 pair + corner) entries -- EE pairs
-//             numbered behind the PT pairs -- stably sorted by vertex with radix_sort_pair_u32, so a vertex's run is in list order; run
-//             starts = exclusive scan of the per-vertex counts (integer atomics).
-//   gather    lane = vertex: sums the scratch contributions (of the gradient or of a product) of its run front to back.  The order is the
-//             list's, so two calls give the same bytes.  A long run (a hub vertex) costs its lane that many loads and nothing else.
+//   energy, incidence, gather: the shared layer of mesh_terms.hip.  The float64 total runs over the PT then the EE energies; the incidence
+//             has the 4 (npt + nee) (vertex, 4 pair + corner) entries, EE pairs numbered behind the PT pairs, built once per pair of lists;
+//             the gather sums a vertex's one run of the scratch contributions (of the gradient or of a product) in list order.
 // Built with -ffp-contract=off (zpc_amd/build.py), as every translation unit behind tri_closest / ee_closest.
 #include <cfloat>
 
@@ -28,7 +24,7 @@
 
 namespace zsr {
 
-constexpr int BAR_BLOCK = 256, RED_CHUNK = 4096;
+constexpr int BAR_BLOCK = TERM_BLOCK;
 
 __global__ __launch_bounds__(256) void barrier_rest_kernel(const float *__restrict__ verts, const int *__restrict__ edges, int ne, float *rest) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_pair_kernel(const BarrierPa
   [[maybe_unused]] FrictionRecord rec = friction_record_zero();
   if (barrier_corners<EE>(a, i, idx, eps)) {
     float p[4][3];
-    pair_rows(a.verts, idx, p);
+    vertex_rows<4>(a.verts, idx, p);
     int status;
     if constexpr (OP == BARRIER_OP_LAG) {
       if constexpr (EE)
@@ -117,7 +113,7 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_pair_kernel(const BarrierPa
       rec = friction_load(a.record, (size_t)i);
       if constexpr (OP == BARRIER_OP_FRICTION_PRODUCT) {
         float x[4][3];
-        pair_rows(a.dir, idx, x);
+        vertex_rows<4>(a.dir, idx, x);
         status = friction_product(rec, p, x, a.mu, a.epsv, g);
       } else if constexpr (OP == BARRIER_OP_FRICTION_GRADIENT) {
         status = friction_gradient(rec, p, a.mu, a.epsv, e, g);
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_pair_kernel(const BarrierPa
       }
     } else if constexpr (PRODUCT) {
       float x[4][3];
-      pair_rows(a.dir, idx, x);
+      vertex_rows<4>(a.dir, idx, x);
       if constexpr (EE)
         status = barrier_ee_hvp<OP == BARRIER_OP_PRODUCT_PSD>(p[0], p[1], p[2], p[3], x, a.dHat2, a.kappa, eps, g);
       else
@@ -146,87 +142,31 @@ __global__ __launch_bounds__(BAR_BLOCK) void barrier_pair_kernel(const BarrierPa
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- the float64 total
-__device__ __forceinline__ double barrier_block_sum(double s) {
-  __shared__ double sm[BAR_BLOCK];
-  sm[threadIdx.x] = s;
-  __syncthreads();
-#pragma unroll
-  for (int h = BAR_BLOCK / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) sm[threadIdx.x] += sm[threadIdx.x + h];
-    __syncthreads();
-  }
-  return sm[0];
-}
-__global__ __launch_bounds__(BAR_BLOCK) void barrier_partial_kernel(const float *__restrict__ a, size_t na, const float *__restrict__ b, size_t nb,
-                                                                    double *partial) {
-  const size_t lo = (size_t)blockIdx.x * RED_CHUNK, n = na + nb;
-  const size_t hi = lo + RED_CHUNK < n ? lo + RED_CHUNK : n;
-  double s = 0.0;
-  for (size_t i = lo + threadIdx.x; i < hi; i += BAR_BLOCK) s += (double)(i < na ? a[i] : b[i - na]);
-  s = barrier_block_sum(s);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-__global__ __launch_bounds__(BAR_BLOCK) void barrier_total_kernel(const double *__restrict__ partial, size_t n, double *total) {
-  double s = 0.0;
-  for (size_t i = threadIdx.x; i < n; i += BAR_BLOCK) s += partial[i];
-  s = barrier_block_sum(s);
-  if (threadIdx.x == 0) *total = s;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- incidence, gradient
-// entry c = 4 pair + corner (EE pairs behind the PT pairs): its vertex as the sort key (nv: an index outside the mesh, sorted behind
-// every vertex and never read), and the per-vertex counts
-__global__ __launch_bounds__(BAR_BLOCK) void barrier_corner_kernel(const int *__restrict__ tris, const int *__restrict__ edges, int nv, int nt, int ne,
-                                                                   const int *__restrict__ ptPairs, int npt, const int *__restrict__ eePairs, int nee,
-                                                                   unsigned *keys, int *vals, unsigned *counts) {
-  const size_t c = (size_t)blockIdx.x * BAR_BLOCK + threadIdx.x;
-  if (c >= 4 * ((size_t)npt + (size_t)nee)) return;
-  const size_t pair = c >> 2;
-  const int k = (int)(c & 3);
-  int v = -1;
-  if (pair < (size_t)npt) {
-    const int vi = ptPairs[2 * pair], ti = ptPairs[2 * pair + 1];
-    if ((unsigned)ti < (unsigned)nt) v = k == 0 ? vi : tris[3 * (size_t)ti + (k - 1)];
-  } else {
+// ---------------------------------------------------------------------------------------------------------------- incidence
+// the vertex of entry c = 4 pair + corner (EE pairs behind the PT pairs); a PT pair's triangle index and an EE pair's edge index are
+// checked before they are followed, the corner's own vertex by incidence_emit
+struct BarrierCornerVertex {
+  const int *tris, *edges;
+  int nt, ne;
+  const int *ptPairs, *eePairs;
+  size_t npt;
+  __device__ int operator()(size_t c) const {
+    const size_t pair = c >> 2;
+    const int k = (int)(c & 3);
+    if (pair < npt) {
+      const int vi = ptPairs[2 * pair], ti = ptPairs[2 * pair + 1];
+      return (unsigned)ti >= (unsigned)nt ? -1 : k == 0 ? vi : tris[3 * (size_t)ti + (k - 1)];
+    }
     const int e = eePairs[2 * (pair - npt) + (k >> 1)];
-    if ((unsigned)e < (unsigned)ne) v = edges[2 * (size_t)e + (k & 1)];
+    return (unsigned)e < (unsigned)ne ? edges[2 * (size_t)e + (k & 1)] : -1;
   }
-  const bool ok = (unsigned)v < (unsigned)nv;
-  keys[c] = ok ? (unsigned)v : (unsigned)nv;
-  vals[c] = (int)c;
-  if (ok) atomicAdd(counts + v, 1u);
-}
-
-__global__ __launch_bounds__(BAR_BLOCK) void barrier_gather_kernel(const int *__restrict__ starts, const int *__restrict__ entries,
-                                                                   const float *__restrict__ contrib, int nv, float *__restrict__ grad) {
-  const int v = blockIdx.x * BAR_BLOCK + threadIdx.x;
-  if (v >= nv) return;
-  const int lo = starts[v], hi = starts[v + 1];
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-  for (int i = lo; i < hi; ++i) {
-    const float *g = contrib + 3 * (size_t)entries[i];
-    s0 += g[0];
-    s1 += g[1];
-    s2 += g[2];
-  }
-  grad[3 * (size_t)v] = s0;
-  grad[3 * (size_t)v + 1] = s1;
-  grad[3 * (size_t)v + 2] = s2;
-}
+};
 
 // the checks the energy, the gradient and the product have in common
 static bool barrier_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const int *ptPairs, size_t npt, const int *eePairs, size_t nee,
                             float dHat, float kappa, int mollify) {
   if (!pol || !m || !m->stats || !(dHat > 0.f && dHat <= FLT_MAX) || !(kappa > 0.f && kappa <= FLT_MAX) || (mollify && !m->hasRest)) return false;
   return barrier_counts_ok(npt, nee) && !(npt && !ptPairs) && !(nee && !eePairs);
-}
-
-// the caller's two zero-distance counts or a temporary, zeroed
-static int *barrier_status(Launch &L, int *status) {
-  int *st = status ? status : (int *)L.temp(sizeof(int) * 2);
-  ZSR_CHECK(hipMemsetAsync(st, 0, sizeof(int) * 2, L.stream));
-  return st;
 }
 
 template <int OP>
@@ -245,9 +185,9 @@ struct FrictionArgs {
 // the pair kernels of one operation: the PT list, then the EE list, whose records follow the PT list's
 static void barrier_launch_pairs(Launch &L, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
                                  size_t nee, float dHat, float kappa, int mollify, int op, const float *dir, float *ptEnergy, float *eeEnergy,
-                                 float *scratch, int *status, const FrictionArgs &fr = {}) {
+                                 float *scratch, int *status, const FrictionArgs &fr) {
   const BarrierPairs pt = {verts ? verts : m->verts, m->tris, (int)m->nv, (int)m->nt, nullptr, ptPairs, (int)npt, dHat * dHat, kappa, dir,
-                           ptEnergy, scratch, barrier_status(L, status), fr.record, fr.mu, fr.epsv};
+                           ptEnergy, scratch, terms_status(L, status), fr.record, fr.mu, fr.epsv};
   BarrierPairs ee = pt;
   ee.prims = m->edges, ee.np = (int)m->ne, ee.rest = mollify ? m->restLen2 : nullptr;
   ee.pairs = eePairs, ee.n = (int)nee, ee.energy = eeEnergy, ee.contrib = scratch ? scratch + 12 * npt : nullptr;
@@ -264,19 +204,44 @@ static void barrier_launch_pairs(Launch &L, const zs_rocm_mesh *m, const float *
   }
 }
 
-// the float64 total of the per-pair energies, PT then EE (mesh.hpp: mesh_elastic.hip sums its per-element energies with it)
-void barrier_launch_total(Launch &L, const float *ptEnergy, size_t npt, const float *eeEnergy, size_t nee, double *total) {
-  const size_t n = npt + nee, parts = (n + RED_CHUNK - 1) / RED_CHUNK;
-  double *partial = parts ? (double *)L.temp(sizeof(double) * parts) : nullptr;
-  if (parts) hipLaunchKernelGGL(barrier_partial_kernel, dim3((unsigned)parts), dim3(BAR_BLOCK), 0, L.stream, ptEnergy, npt, eeEnergy, nee, partial);
-  hipLaunchKernelGGL(barrier_total_kernel, dim3(1), dim3(BAR_BLOCK), 0, L.stream, partial, parts, total);
-}
-
 // the checks the friction evaluations have in common
 static bool friction_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs,
                              size_t nee, const float *record, float mu, float epsv) {
   if (!pol || !m || !m->stats || !(mu >= 0.f && mu <= FLT_MAX) || !(epsv > 0.f && epsv <= FLT_MAX) || (m->nv && !u)) return false;
   return barrier_counts_ok(npt, nee) && !(npt && !ptPairs) && !(nee && !eePairs) && !(npt + nee && !record);
+}
+
+// the launch names of the operations, in the order of BARRIER_OP_*
+static const char *const BARRIER_OP_NAME[] = {"mesh_barrier_energy", "mesh_barrier_gradient", "mesh_barrier_hessian_product",
+                                              "mesh_barrier_hessian_product", "mesh_friction_lag", "mesh_friction_energy",
+                                              "mesh_friction_gradient", "mesh_friction_hessian_product"};
+
+// what the barrier and friction entries share behind their argument checks.  verts: the positions, or the displacement of a friction
+// evaluation (fr set).  Energy (grad == NULL) or energy and gradient:
+static int pairs_evaluate(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
+                          size_t nee, float dHat, float kappa, int mollify, int op, const FrictionArgs &fr, const int *starts, const int *entries,
+                          float *scratch, float *ptEnergy, float *eeEnergy, double *total, float *grad, int *status) {
+  if (grad && m->nv && (!starts || (npt + nee && (!entries || !scratch)))) return -1;
+  Launch L(pol, BARRIER_OP_NAME[op]);
+  if (npt && !ptEnergy) ptEnergy = (float *)L.temp(sizeof(float) * npt);
+  if (nee && !eeEnergy) eeEnergy = (float *)L.temp(sizeof(float) * nee);
+  barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, op, nullptr, ptEnergy, eeEnergy, grad ? scratch : nullptr,
+                       status, fr);
+  if (total) terms_total(L, ptEnergy, npt, eeEnergy, nee, total);
+  const TermRun run = {starts, entries, scratch};
+  if (grad) terms_gather(L, &run, 1, m->nv, grad);
+  return 0;
+}
+// ... and the Hessian-vector product:
+static int pairs_product(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
+                         size_t nee, float dHat, float kappa, int mollify, int op, const FrictionArgs &fr, const float *x, const int *starts,
+                         const int *entries, float *scratch, float *hx, int *status) {
+  if (m->nv && (!x || !hx || !starts || (npt + nee && (!entries || !scratch)))) return -1;
+  Launch L(pol, BARRIER_OP_NAME[op]);
+  barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, op, x, nullptr, nullptr, scratch, status, fr);
+  const TermRun run = {starts, entries, scratch};
+  terms_gather(L, &run, 1, m->nv, hx);
+  return 0;
 }
 
 }  // namespace zsr
@@ -320,120 +285,64 @@ int zs_rocm_mesh_barrier_incidence(zs_rocm_policy *pol, const zs_rocm_mesh *m, c
   const size_t n = 4 * (npt + nee);
   if (n && !entries) return -1;
   Launch L(pol, "mesh_barrier_incidence");
-  unsigned *counts = (unsigned *)L.temp(sizeof(unsigned) * (m->nv + 1));
-  ZSR_CHECK(hipMemsetAsync(counts, 0, sizeof(unsigned) * (m->nv + 1), L.stream));
-  if (n) {
-    unsigned *keys = (unsigned *)L.temp(sizeof(unsigned) * n), *sorted = (unsigned *)L.temp(sizeof(unsigned) * n);
-    int *vals = (int *)L.temp(sizeof(int) * n);
-    hipLaunchKernelGGL(barrier_corner_kernel, dim3(ceil_div(n, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, m->tris, m->edges, (int)m->nv, (int)m->nt,
-                       (int)m->ne, ptPairs, (int)npt, eePairs, (int)nee, keys, vals, counts);
-    int bits = 1;
-    while (bits < 32 && ((size_t)1 << bits) <= m->nv) ++bits;  // the keys are 0 .. nv
-    radix_sort_pair_u32(L, keys, vals, sorted, entries, n, 0, bits);
-  }
-  exclusive_scan_u32(L, counts, m->nv + 1, (unsigned *)starts);
-  return 0;
-}
-
-// the shared entry: grad == NULL is energy only
-static int barrier_run(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs, size_t nee,
-                       float dHat, float kappa, int mollify, const int *starts, const int *entries, float *scratch, float *ptEnergy,
-                       float *eeEnergy, double *total, float *grad, int *status) {
-  if (!barrier_args_ok(pol, m, ptPairs, npt, eePairs, nee, dHat, kappa, mollify)) return -1;
-  if (grad && m->nv && (!starts || (npt + nee && (!entries || !scratch)))) return -1;
-  Launch L(pol, grad ? "mesh_barrier_gradient" : "mesh_barrier_energy");
-  if (npt && !ptEnergy) ptEnergy = (float *)L.temp(sizeof(float) * npt);
-  if (nee && !eeEnergy) eeEnergy = (float *)L.temp(sizeof(float) * nee);
-  barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, grad ? BARRIER_OP_GRADIENT : BARRIER_OP_ENERGY, nullptr,
-                       ptEnergy, eeEnergy, grad ? scratch : nullptr, status);
-  if (total) barrier_launch_total(L, ptEnergy, npt, eeEnergy, nee, total);
-  if (grad && m->nv)
-    hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
-                       grad);
+  incidence_build(L, BarrierCornerVertex{m->tris, m->edges, (int)m->nt, (int)m->ne, ptPairs, eePairs, npt}, n, m->nv, starts, entries);
   return 0;
 }
 
 int zs_rocm_mesh_barrier_energy(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
                                 size_t nee, float dHat, float kappa, int mollify, float *ptEnergy, float *eeEnergy, double *total, int *status) {
-  return barrier_run(pol, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, nullptr, nullptr, nullptr, ptEnergy, eeEnergy, total, nullptr,
-                     status);
+  if (!barrier_args_ok(pol, m, ptPairs, npt, eePairs, nee, dHat, kappa, mollify)) return -1;
+  return pairs_evaluate(pol, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, BARRIER_OP_ENERGY, {}, nullptr, nullptr, nullptr, ptEnergy,
+                        eeEnergy, total, nullptr, status);
 }
 
 int zs_rocm_mesh_barrier_gradient(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
                                   size_t nee, float dHat, float kappa, int mollify, const int *starts, const int *entries, float *scratch,
                                   float *ptEnergy, float *eeEnergy, double *total, float *grad, int *status) {
-  if (!grad && m && m->nv) return -1;
-  return barrier_run(pol, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, starts, entries, scratch, ptEnergy, eeEnergy, total, grad,
-                     status);
+  if (!barrier_args_ok(pol, m, ptPairs, npt, eePairs, nee, dHat, kappa, mollify) || (!grad && m->nv)) return -1;
+  return pairs_evaluate(pol, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, grad ? BARRIER_OP_GRADIENT : BARRIER_OP_ENERGY, {}, starts,
+                        entries, scratch, ptEnergy, eeEnergy, total, grad, status);
 }
 
 int zs_rocm_mesh_barrier_hessian_product(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt,
                                          const int *eePairs, size_t nee, float dHat, float kappa, int mollify, int psd, const float *x,
                                          const int *starts, const int *entries, float *scratch, float *hx, int *status) {
   if (!barrier_args_ok(pol, m, ptPairs, npt, eePairs, nee, dHat, kappa, mollify)) return -1;
-  if (m->nv && (!x || !hx || !starts || (npt + nee && (!entries || !scratch)))) return -1;
-  Launch L(pol, "mesh_barrier_hessian_product");
-  barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, psd ? BARRIER_OP_PRODUCT_PSD : BARRIER_OP_PRODUCT, x, nullptr,
-                       nullptr, scratch, status);
-  if (m->nv)
-    hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
-                       hx);
-  return 0;
+  return pairs_product(pol, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, psd ? BARRIER_OP_PRODUCT_PSD : BARRIER_OP_PRODUCT, {}, x,
+                       starts, entries, scratch, hx, status);
 }
 
 int zs_rocm_mesh_friction_lag(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
                               size_t nee, float dHat, float kappa, int mollify, float *record, int *status) {
   if (!barrier_args_ok(pol, m, ptPairs, npt, eePairs, nee, dHat, kappa, mollify) || (npt + nee && !record)) return -1;
-  Launch L(pol, "mesh_friction_lag");
+  Launch L(pol, BARRIER_OP_NAME[BARRIER_OP_LAG]);
   barrier_launch_pairs(L, m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, BARRIER_OP_LAG, nullptr, nullptr, nullptr, nullptr, status,
                        {record, 0.f, 0.f});
-  return 0;
-}
-
-// the shared entry: grad == NULL is energy only
-static int friction_run(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs, size_t nee,
-                        const float *record, float mu, float epsv, const int *starts, const int *entries, float *scratch, float *ptEnergy,
-                        float *eeEnergy, double *total, float *grad, int *status) {
-  if (!friction_args_ok(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv)) return -1;
-  if (grad && m->nv && (!starts || (npt + nee && (!entries || !scratch)))) return -1;
-  Launch L(pol, grad ? "mesh_friction_gradient" : "mesh_friction_energy");
-  if (npt && !ptEnergy) ptEnergy = (float *)L.temp(sizeof(float) * npt);
-  if (nee && !eeEnergy) eeEnergy = (float *)L.temp(sizeof(float) * nee);
-  barrier_launch_pairs(L, m, u, ptPairs, npt, eePairs, nee, 0.f, 0.f, 0, grad ? BARRIER_OP_FRICTION_GRADIENT : BARRIER_OP_FRICTION_ENERGY, nullptr,
-                       ptEnergy, eeEnergy, grad ? scratch : nullptr, status, {const_cast<float *>(record), mu, epsv});
-  if (total) barrier_launch_total(L, ptEnergy, npt, eeEnergy, nee, total);
-  if (grad && m->nv)
-    hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
-                       grad);
   return 0;
 }
 
 int zs_rocm_mesh_friction_energy(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs,
                                  size_t nee, const float *record, float mu, float epsv, float *ptEnergy, float *eeEnergy, double *total,
                                  int *status) {
-  return friction_run(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv, nullptr, nullptr, nullptr, ptEnergy, eeEnergy, total, nullptr,
-                      status);
+  if (!friction_args_ok(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv)) return -1;
+  return pairs_evaluate(pol, m, u, ptPairs, npt, eePairs, nee, 0.f, 0.f, 0, BARRIER_OP_FRICTION_ENERGY, {const_cast<float *>(record), mu, epsv},
+                        nullptr, nullptr, nullptr, ptEnergy, eeEnergy, total, nullptr, status);
 }
 
 int zs_rocm_mesh_friction_gradient(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs,
                                    size_t nee, const float *record, float mu, float epsv, const int *starts, const int *entries, float *scratch,
                                    float *ptEnergy, float *eeEnergy, double *total, float *grad, int *status) {
-  if (!grad && m && m->nv) return -1;
-  return friction_run(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv, starts, entries, scratch, ptEnergy, eeEnergy, total, grad, status);
+  if (!friction_args_ok(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv) || (!grad && m->nv)) return -1;
+  return pairs_evaluate(pol, m, u, ptPairs, npt, eePairs, nee, 0.f, 0.f, 0, grad ? BARRIER_OP_FRICTION_GRADIENT : BARRIER_OP_FRICTION_ENERGY,
+                        {const_cast<float *>(record), mu, epsv}, starts, entries, scratch, ptEnergy, eeEnergy, total, grad, status);
 }
 
 int zs_rocm_mesh_friction_hessian_product(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const float *x, const int *ptPairs, size_t npt,
                                           const int *eePairs, size_t nee, const float *record, float mu, float epsv, const int *starts,
                                           const int *entries, float *scratch, float *hx, int *status) {
   if (!friction_args_ok(pol, m, u, ptPairs, npt, eePairs, nee, record, mu, epsv)) return -1;
-  if (m->nv && (!x || !hx || !starts || (npt + nee && (!entries || !scratch)))) return -1;
-  Launch L(pol, "mesh_friction_hessian_product");
-  barrier_launch_pairs(L, m, u, ptPairs, npt, eePairs, nee, 0.f, 0.f, 0, BARRIER_OP_FRICTION_PRODUCT, x, nullptr, nullptr, scratch, status,
-                       {const_cast<float *>(record), mu, epsv});
-  if (m->nv)
-    hipLaunchKernelGGL(barrier_gather_kernel, dim3(ceil_div(m->nv, BAR_BLOCK)), dim3(BAR_BLOCK), 0, L.stream, starts, entries, scratch, (int)m->nv,
-                       hx);
-  return 0;
+  return pairs_product(pol, m, u, ptPairs, npt, eePairs, nee, 0.f, 0.f, 0, BARRIER_OP_FRICTION_PRODUCT, {const_cast<float *>(record), mu, epsv}, x,
+                       starts, entries, scratch, hx, status);
 }
 
 }  // extern "C"

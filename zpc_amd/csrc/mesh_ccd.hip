@@ -70,8 +70,8 @@ __global__ __launch_bounds__(CCD_BLOCK) void ccd_kernel(const CcdPairs a) {
       r.s.t = a.tMax;
       if (pair_corners<EE>(a.pairs, a.prims, a.nv, a.np, i, idx)) {
         float x[4][3], p[4][3];
-        pair_rows(a.verts, idx, x);
-        pair_rows(a.dir, idx, p);
+        vertex_rows<4>(a.verts, idx, x);
+        vertex_rows<4>(a.dir, idx, p);
         live = !ccd_start<EE>(x, p, a.slack, a.tMax, r.s, status);
       }
       if (!live) ccd_finish<EE>(a, r, status, best);
@@ -97,8 +97,8 @@ __global__ __launch_bounds__(CCD_BLOCK) void ccd_kernel(const CcdPairs a) {
       int idx[4], status = CCD_OK;
       pair_corners<EE>(a.pairs, a.prims, a.nv, a.np, r.pair, idx);  // an active pair: it passed this test in phase 1
       float x[4][3], p[4][3];
-      pair_rows(a.verts, idx, x);
-      pair_rows(a.dir, idx, p);
+      vertex_rows<4>(a.verts, idx, x);
+      vertex_rows<4>(a.dir, idx, p);
       bool done = false;
 #pragma unroll 1
       for (int k = 0; k < CCD_ROUND && !done; ++k) done = ccd_step<EE>(x, p, a.tMax, a.maxIter, r.s, status);

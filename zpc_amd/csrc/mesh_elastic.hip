@@ -4,8 +4,8 @@
 //
 //   rest      zs_rocm_mesh_set_rest_shape.  Topology, once: a run of exactly two equal keys in the mesh's sorted half-edge keys is a hinge
 //             (flags -> scan -> compact, so hinges are in unique-edge order; the run is in triangle order, the sort being stable); longer
-//             runs are counted as non-manifold.  The hinge incidence is the barrier's: 4 nh (vertex, 4 hinge + corner) entries stably
-//             sorted by vertex with radix_sort_pair_u32, run starts from a scan of the per-vertex counts.  The triangle incidence is the
+//             runs are counted as non-manifold.  The hinge incidence is the shared one of mesh_terms.hip over the 4 nh (vertex,
+//             4 hinge + corner) entries.  The triangle incidence is the
 //             mesh's own cornerKeys / cornerVals; only its run starts are added (a binary search per vertex).  Positions, every call: the
 //             triangle and hinge records, degenerate ones zeroed and counted, and the vertex areas (lane = vertex, a third of each
 //             incident rest area, summed in corner order).
@@ -13,8 +13,8 @@
 //             barrier_pair_kernel.  Every vertex index is checked before its load (an index outside the mesh: the element is idle).  The
 //             kernel writes the element's energy and / or its [3][3] or [4][3] terms to a scratch array once, hinges behind the triangles.
 //             Elements whose result leaves the float range are counted with an integer atomic and contribute exactly zero.
-//   energy    the float64 fixed-order sum of the float32 element energies, triangles then hinges: the barrier's two reduction kernels.
-//   gather    lane = vertex: sums the scratch terms of its triangle run front to back, then those of its hinge run.
+//   energy    the float64 fixed-order sum of the float32 element energies, triangles then hinges (terms_total of mesh_terms.hip).
+//   gather    terms_gather over two runs per vertex: the scratch terms of its triangle run front to back, then those of its hinge run.
 // mu = lam = 0 skips the membrane launch and kb = 0 the bending launch: their energies and terms are zero bytes.
 // Built with -ffp-contract=off (zpc_amd/build.py): tests/ref64_elastic.py replays the float32 chain operation by operation.
 #include <cfloat>
@@ -24,7 +24,7 @@
 
 namespace zsr {
 
-constexpr int EL_BLOCK = 256;
+constexpr int EL_BLOCK = TERM_BLOCK;
 
 // ---------------------------------------------------------------------------------------------------------------- the rest pass
 // flags[i] = 1 where sorted half-edge i starts a run of exactly two keys of a proper edge; runs of more than two are counted
@@ -58,17 +58,11 @@ __global__ __launch_bounds__(EL_BLOCK) void elastic_hinge_compact_kernel(const u
   o[2] = tris[h0 / 3 * 3 + (h0 % 3 + 2) % 3];
   o[3] = tris[h1 / 3 * 3 + (h1 % 3 + 2) % 3];
 }
-// entry c = 4 hinge + corner: its vertex as the sort key (nv: an index outside the mesh, sorted behind every vertex and never read)
-__global__ __launch_bounds__(EL_BLOCK) void elastic_hinge_corner_kernel(const int *__restrict__ hinges, size_t n4, int nv, unsigned *keys, int *vals,
-                                                                        unsigned *counts) {
-  const size_t c = (size_t)blockIdx.x * EL_BLOCK + threadIdx.x;
-  if (c >= n4) return;
-  const int v = hinges[c];
-  const bool ok = (unsigned)v < (unsigned)nv;
-  keys[c] = ok ? (unsigned)v : (unsigned)nv;
-  vals[c] = (int)c;
-  if (ok) atomicAdd(counts + v, 1u);
-}
+// the vertex of incidence entry c = 4 hinge + corner
+struct HingeCornerVertex {
+  const int *hinges;
+  __device__ int operator()(size_t c) const { return hinges[c]; }
+};
 // starts[v] = the first sorted corner whose key is not below v, v = 0 .. nv
 __global__ __launch_bounds__(EL_BLOCK) void elastic_corner_starts_kernel(const unsigned *__restrict__ keys, size_t n3, int nv, int *starts) {
   const int v = blockIdx.x * EL_BLOCK + threadIdx.x;
@@ -92,13 +86,6 @@ __device__ __forceinline__ bool elastic_indices(const int *__restrict__ elems, s
   }
   return ok;
 }
-template <int N>
-__device__ __forceinline__ void elastic_rows(const float *__restrict__ src, const int (&idx)[N], float (&out)[N][3]) {
-#pragma unroll
-  for (int k = 0; k < N; ++k)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) out[k][d] = src[3 * (size_t)idx[k] + d];
-}
 
 // the rest record of element i (16-byte records in a 256-byte aligned array); degenerate ones are counted
 template <bool HINGE>
@@ -112,7 +99,7 @@ __global__ __launch_bounds__(EL_BLOCK) void elastic_rest_kernel(const float *__r
   int status = ELASTIC_DEGENERATE;
   if (elastic_indices<N>(elems, (size_t)i, nv, idx)) {
     float X[N][3];
-    elastic_rows<N>(verts, idx, X);
+    vertex_rows<N>(verts, idx, X);
     if constexpr (HINGE)
       status = elastic_hinge_rest(X[0], X[1], X[2], X[3], rec);
     else
@@ -160,20 +147,20 @@ __global__ __launch_bounds__(EL_BLOCK) void elastic_elem_kernel(const ElasticEle
     int status;
     if constexpr (HINGE) {
       if constexpr (PRODUCT) {  // H does not depend on the positions
-        elastic_rows<N>(a.dir, idx, x);
+        vertex_rows<N>(a.dir, idx, x);
         status = elastic_hinge_product(rec, x, a.kb, t);
       } else {
-        elastic_rows<N>(a.verts, idx, x);
+        vertex_rows<N>(a.verts, idx, x);
         if constexpr (OP == ELASTIC_OP_GRADIENT)
           status = elastic_hinge_gradient(rec, x, a.kb, e, t);
         else
           status = elastic_hinge_energy(rec, x, a.kb, e);
       }
     } else {
-      elastic_rows<N>(a.verts, idx, x);
+      vertex_rows<N>(a.verts, idx, x);
       if constexpr (PRODUCT) {
         float z[N][3];
-        elastic_rows<N>(a.dir, idx, z);
+        vertex_rows<N>(a.dir, idx, z);
         status = elastic_tri_product<OP == ELASTIC_OP_PRODUCT_PSD>(rec, x, z, a.mu, a.lam, t);
       } else if constexpr (OP == ELASTIC_OP_GRADIENT) {
         status = elastic_tri_gradient(rec, x, a.mu, a.lam, e, t);
@@ -193,31 +180,6 @@ __global__ __launch_bounds__(EL_BLOCK) void elastic_elem_kernel(const ElasticEle
   }
 }
 
-// lane = vertex: the terms of its triangle run (entries 3 t + corner into triTerms), then of its hinge run (4 h + corner into hingeTerms)
-__global__ __launch_bounds__(EL_BLOCK) void elastic_gather_kernel(const int *__restrict__ cornerStarts, const int *__restrict__ cornerVals,
-                                                                  const float *__restrict__ triTerms, const int *__restrict__ hingeStarts,
-                                                                  const int *__restrict__ hingeEntries, const float *__restrict__ hingeTerms, int nv,
-                                                                  float *__restrict__ out) {
-  const int v = blockIdx.x * EL_BLOCK + threadIdx.x;
-  if (v >= nv) return;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-  for (int i = cornerStarts[v]; i < cornerStarts[v + 1]; ++i) {
-    const float *g = triTerms + 3 * (size_t)cornerVals[i];
-    s0 += g[0];
-    s1 += g[1];
-    s2 += g[2];
-  }
-  for (int i = hingeStarts[v]; i < hingeStarts[v + 1]; ++i) {
-    const float *g = hingeTerms + 3 * (size_t)hingeEntries[i];
-    s0 += g[0];
-    s1 += g[1];
-    s2 += g[2];
-  }
-  out[3 * (size_t)v] = s0;
-  out[3 * (size_t)v + 1] = s1;
-  out[3 * (size_t)v + 2] = s2;
-}
-
 template <int OP>
 static void elastic_launch_op(Launch &L, const ElasticElems &tri, bool membrane, const ElasticElems &hinge, bool bending) {
   const dim3 block(EL_BLOCK);
@@ -234,8 +196,7 @@ static bool elastic_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, fl
 // gets zero bytes
 static void elastic_launch(Launch &L, const zs_rocm_mesh *m, const float *verts, float mu, float lam, float kb, int op, const float *dir,
                            float *triEnergy, float *hingeEnergy, float *scratch, int *status) {
-  int *st = status ? status : (int *)L.temp(sizeof(int) * 2);
-  ZSR_CHECK(hipMemsetAsync(st, 0, sizeof(int) * 2, L.stream));
+  int *st = terms_status(L, status);
   const bool membrane = mu > 0.f || lam > 0.f, bending = kb > 0.f;
   const ElasticElems tri = {verts ? verts : m->verts, m->tris, (int)m->nv, (int)m->nt, m->triRecord, mu, lam, kb, dir, triEnergy, scratch, st};
   ElasticElems hinge = tri;
@@ -257,10 +218,10 @@ static void elastic_launch(Launch &L, const zs_rocm_mesh *m, const float *verts,
   }
 }
 
+// per vertex the terms of its triangle run (entries 3 t + corner), then of its hinge run (4 h + corner, behind the triangles' terms)
 static void elastic_launch_gather(Launch &L, const zs_rocm_mesh *m, const float *scratch, float *out) {
-  if (m->nv)
-    hipLaunchKernelGGL(elastic_gather_kernel, dim3(ceil_div(m->nv, EL_BLOCK)), dim3(EL_BLOCK), 0, L.stream, m->cornerStarts, m->cornerVals, scratch,
-                       m->hingeStarts, m->hingeEntries, scratch + 9 * m->nt, (int)m->nv, out);
+  const TermRun runs[2] = {{m->cornerStarts, m->cornerVals, scratch}, {m->hingeStarts, m->hingeEntries, scratch + 9 * m->nt}};
+  terms_gather(L, runs, 2, m->nv, out);
 }
 
 // the hinges, their incidence and the run starts of the corner incidence: the first call only
@@ -278,7 +239,7 @@ static void elastic_topology(Launch &L, zs_rocm_mesh &m) {
     ZSR_CHECK(hipStreamSynchronize(L.stream));
   }
   m.nh = nh;
-  const size_t nh1 = nh ? nh : 1, n4 = 4 * (size_t)nh;
+  const size_t nh1 = nh ? nh : 1;
   ZSR_CHECK(hipMalloc((void **)&m.hinges, sizeof(int) * 4 * nh1));
   ZSR_CHECK(hipMalloc((void **)&m.hingeRecord, sizeof(float) * 4 * nh1));
   ZSR_CHECK(hipMalloc((void **)&m.hingeEntries, sizeof(int) * 4 * nh1));
@@ -287,17 +248,7 @@ static void elastic_topology(Launch &L, zs_rocm_mesh &m) {
   ZSR_CHECK(hipMalloc((void **)&m.triRecord, sizeof(float) * 4 * (m.nt ? m.nt : 1)));
   ZSR_CHECK(hipMalloc((void **)&m.vertArea, sizeof(float) * (nv ? nv : 1)));
   if (nh) hipLaunchKernelGGL(elastic_hinge_compact_kernel, dim3(ceil_div(n3, EL_BLOCK)), dim3(EL_BLOCK), 0, L.stream, m.heKeys, m.heVals, n3, flags, offsets, m.tris, m.hinges);
-  unsigned *counts = (unsigned *)L.temp(sizeof(unsigned) * (nv + 1));
-  ZSR_CHECK(hipMemsetAsync(counts, 0, sizeof(unsigned) * (nv + 1), L.stream));
-  if (n4) {
-    unsigned *keys = (unsigned *)L.temp(sizeof(unsigned) * n4), *sorted = (unsigned *)L.temp(sizeof(unsigned) * n4);
-    int *vals = (int *)L.temp(sizeof(int) * n4);
-    hipLaunchKernelGGL(elastic_hinge_corner_kernel, dim3(ceil_div(n4, EL_BLOCK)), dim3(EL_BLOCK), 0, L.stream, m.hinges, n4, (int)nv, keys, vals, counts);
-    int bits = 1;
-    while (bits < 32 && ((size_t)1 << bits) <= nv) ++bits;  // the keys are 0 .. nv
-    radix_sort_pair_u32(L, keys, vals, sorted, m.hingeEntries, n4, 0, bits);
-  }
-  exclusive_scan_u32(L, counts, nv + 1, (unsigned *)m.hingeStarts);
+  incidence_build(L, HingeCornerVertex{m.hinges}, 4 * (size_t)nh, nv, m.hingeStarts, m.hingeEntries);
   hipLaunchKernelGGL(elastic_corner_starts_kernel, dim3(ceil_div(nv + 1, EL_BLOCK)), dim3(EL_BLOCK), 0, L.stream, m.cornerKeys, n3, (int)nv, m.cornerStarts);
   m.hasHinges = true;
 }
@@ -360,7 +311,7 @@ static int elastic_run(zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *
   if (m->nh && !hingeEnergy) hingeEnergy = (float *)L.temp(sizeof(float) * m->nh);
   elastic_launch(L, m, verts, mu, lam, kb, grad ? ELASTIC_OP_GRADIENT : ELASTIC_OP_ENERGY, nullptr, triEnergy, hingeEnergy, grad ? scratch : nullptr,
                  status);
-  if (total) barrier_launch_total(L, triEnergy, m->nt, hingeEnergy, m->nh, total);
+  if (total) terms_total(L, triEnergy, m->nt, hingeEnergy, m->nh, total);
   if (grad) elastic_launch_gather(L, m, scratch, grad);
   return 0;
 }

@@ -70,6 +70,21 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _positive_f32(who, name, x):
+    """x as a float: finite, positive and still both as a float32"""
+    x = float(x)
+    if not (np.isfinite(x) and x > 0 and np.float32(x) > 0 and np.isfinite(np.float32(x))):
+        raise ValueError("TriMesh.%s: %s must be finite and positive" % (who, name))
+    return x
+
+
+def _pair_lists(prox):
+    """the contiguous PT and EE lists of a Proximity (None for a side it does not have) and their counts"""
+    pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
+    ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
+    return pt, ee, (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+
+
 class _ProximityState:
     """room on a Proximity for what the library keeps with it (the incidence of TriMesh.barrier), next to its public fields"""
 
@@ -271,9 +286,7 @@ class TriMesh:
     def proximity(self, dhat, pt=True, ee=True):
         """the vertex-triangle and edge-edge pairs of the mesh with itself closer than dhat, without topological neighbours (a triangle
         that contains the vertex, edges that share a vertex): a Proximity.  The lists are in a fixed order: two calls give the same bytes."""
-        dhat = float(dhat)
-        if not (np.isfinite(dhat) and dhat > 0 and np.float32(dhat) > 0 and np.isfinite(np.float32(dhat))):
-            raise ValueError("TriMesh.proximity: dhat must be finite and positive")
+        dhat = _positive_f32("proximity", "dhat", dhat)
         r = Proximity()
         L = lib()
         if pt:
@@ -287,10 +300,8 @@ class TriMesh:
     def set_rest(self, verts=None):
         """stores the squared rest length of every unique edge (the threshold of the edge-edge mollifier) from verts [nv, 3], or from the
         mesh's current vertices"""
-        v = None if verts is None else _dev_f32(verts, 3)
-        if v is not None and v.shape[0] != self.nv:
-            raise ValueError("TriMesh.set_rest: [nv, 3] positions on the same topology")
-        if lib().zs_rocm_mesh_set_rest(self.pol.handle, self._h, None if v is None else v.data_ptr()) != 0:
+        v = self._trial("set_rest", verts)
+        if lib().zs_rocm_mesh_set_rest(self.pol.handle, self._h, _ptr(v)) != 0:
             raise RuntimeError("zs_rocm_mesh_set_rest failed")
         self.pol.syncCtx()
         self.has_rest = True
@@ -314,8 +325,8 @@ class TriMesh:
                 raise ValueError("TriMesh.barrier: too many pairs")
             starts = torch.empty(sizes[0], dtype=torch.int32, device="cuda")
             entries = torch.empty(sizes[1], dtype=torch.int32, device="cuda")
-            if lib().zs_rocm_mesh_barrier_incidence(self.pol.handle, self._h, None if pt is None else pt.data_ptr(), npt,
-                                                    None if ee is None else ee.data_ptr(), nee, starts.data_ptr(), entries.data_ptr()) != 0:
+            if lib().zs_rocm_mesh_barrier_incidence(self.pol.handle, self._h, _ptr(pt), npt, _ptr(ee), nee, starts.data_ptr(),
+                                                    entries.data_ptr()) != 0:
                 raise RuntimeError("zs_rocm_mesh_barrier_incidence failed")
             self.pol.syncCtx()
             prox._incidence = (starts, entries, int(sizes[2]))
@@ -324,53 +335,65 @@ class TriMesh:
     def _barrier_args(self, who, prox, dhat, kappa, verts, mollify):
         """what barrier and barrier_hessian_product (who, for the messages) share: the arguments checked; returns the trial positions or None,
         the contiguous lists, their counts and the head of the C call up to mollify"""
-        dhat, kappa = float(dhat), float(kappa)
-        for name, x in (("dhat", dhat), ("kappa", kappa)):
-            if not (np.isfinite(x) and x > 0 and np.float32(x) > 0 and np.isfinite(np.float32(x))):
-                raise ValueError("TriMesh.%s: %s must be finite and positive" % (who, name))
+        dhat, kappa = _positive_f32(who, "dhat", dhat), _positive_f32(who, "kappa", kappa)
         if mollify and not getattr(self, "has_rest", False):
             raise ValueError("TriMesh.%s: mollify=True needs the rest lengths, call set_rest first" % who)
         if not isinstance(prox, Proximity):
             raise ValueError("TriMesh.%s: prox is the result of TriMesh.proximity" % who)
+        v = self._trial(who, verts)
+        pt, ee, npt, nee = _pair_lists(prox)
+        return v, pt, ee, npt, nee, (self.pol.handle, self._h, _ptr(v), _ptr(pt), npt, _ptr(ee), nee, dhat, kappa, 1 if mollify else 0)
+
+    def _trial(self, who, verts):
+        """trial positions on the device, or None"""
         v = None if verts is None else _dev_f32(verts, 3)
         if v is not None and v.shape[0] != self.nv:
             raise ValueError("TriMesh.%s: verts are [nv, 3] positions on the same topology" % who)
-        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
-        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
-        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
-        return v, pt, ee, npt, nee, (self.pol.handle, self._h, _ptr(v), _ptr(pt), npt, _ptr(ee), nee, dhat, kappa, 1 if mollify else 0)
+        return v
 
-    def _zero_distance(self, status):
-        """waits for the call and returns the (PT, EE) pairs it counted at zero distance"""
+    def _direction(self, who, direction, name="direction", kind="array"):
+        d = _dev_f32(direction, 3)
+        if d.shape[0] != self.nv:
+            raise ValueError("TriMesh.%s: %s is an [nv, 3] %s" % (who, name, kind))
+        return d
+
+    def _counts(self, status):
+        """waits for the call and returns the counts it left in its status words"""
         self.pol.syncCtx()
-        z = status.tolist()
-        return int(z[0]), int(z[1])
+        return tuple(int(z) for z in status.tolist())
+
+    def _evaluate(self, r, what, head, sides, terms=None):
+        """energy and optional gradient of one term (what: barrier, friction, elastic) into the result r: allocates r.energy, the two
+        per-element energies sides = ((field, count or None for a side that is skipped), ..) and, for a gradient, r.grad; terms = (the
+        incidence tensors that follow head in the C call.., the size of the scratch array), None: energy only.  Returns the two counts of
+        the status word and the scratch array"""
+        import torch
+        f32 = dict(dtype=torch.float32, device="cuda")
+        r.energy = torch.empty((), dtype=torch.float64, device="cuda")
+        for field, n in sides:
+            setattr(r, field, None if n is None else torch.empty(n, **f32))
+        tail = tuple(_ptr(getattr(r, field)) for field, _ in sides) + (r.energy.data_ptr(),)
+        status = torch.empty(2, dtype=torch.int32, device="cuda")
+        r.grad = scratch = None
+        if terms is None:
+            rc = getattr(lib(), "zs_rocm_mesh_%s_energy" % what)(*head, *tail, status.data_ptr())
+        else:
+            scratch, r.grad = torch.empty(terms[-1], **f32), torch.empty(self.nv, 3, **f32)
+            rc = getattr(lib(), "zs_rocm_mesh_%s_gradient" % what)(*head, *(t.data_ptr() for t in terms[:-1]), scratch.data_ptr(), *tail,
+                                                                   r.grad.data_ptr(), status.data_ptr())
+        if rc != 0:
+            raise RuntimeError("the %s call failed" % what)
+        return self._counts(status), scratch
 
     def barrier(self, prox, dhat, kappa, verts=None, mollify=True, gradient=True):
         """the IPC barrier potential -kappa (d2 - dhat^2)^2 log(d2 / dhat^2) summed over the pairs of prox (a Proximity of this mesh; a side
         that is None is skipped), and its gradient: a Barrier.  verts [nv, 3]: trial positions on the same topology instead of the mesh's
         own; distances are recomputed there, the lists stay as they are.  mollify: edge-edge pairs are multiplied by the mollifier of
         nearly parallel edges, which needs set_rest.  Two calls give the same bytes."""
-        import torch
         v, pt, ee, npt, nee, head = self._barrier_args("barrier", prox, dhat, kappa, verts, mollify)
         r = Barrier()
-        r.energy = torch.empty((), dtype=torch.float64, device="cuda")
-        r.pt_energy = None if pt is None else torch.empty(npt, dtype=torch.float32, device="cuda")
-        r.ee_energy = None if ee is None else torch.empty(nee, dtype=torch.float32, device="cuda")
-        r.grad = None
-        status = torch.empty(2, dtype=torch.int32, device="cuda")
-        tail = (_ptr(r.pt_energy), _ptr(r.ee_energy), r.energy.data_ptr())
-        if gradient:
-            starts, entries, nscratch = self._incidence(prox, pt, ee)
-            scratch = torch.empty(nscratch, dtype=torch.float32, device="cuda")
-            r.grad = torch.empty(self.nv, 3, dtype=torch.float32, device="cuda")
-            rc = lib().zs_rocm_mesh_barrier_gradient(*head, starts.data_ptr(), entries.data_ptr(), scratch.data_ptr(), *tail, r.grad.data_ptr(),
-                                                     status.data_ptr())
-        else:
-            rc = lib().zs_rocm_mesh_barrier_energy(*head, *tail, status.data_ptr())
-        if rc != 0:
-            raise RuntimeError("the barrier call failed")
-        r.zero_distance = self._zero_distance(status)
+        sides = (("pt_energy", None if pt is None else npt), ("ee_energy", None if ee is None else nee))
+        r.zero_distance, _ = self._evaluate(r, "barrier", head, sides, self._incidence(prox, pt, ee) if gradient else None)
         return r
 
     def barrier_hessian_product(self, prox, dhat, kappa, x, verts=None, mollify=True, psd=False):
@@ -380,9 +403,7 @@ class TriMesh:
         conjugate-gradient solve can use.  Two calls give the same bytes."""
         import torch
         v, pt, ee, npt, nee, head = self._barrier_args("barrier_hessian_product", prox, dhat, kappa, verts, mollify)
-        d = _dev_f32(x, 3)
-        if d.shape[0] != self.nv:
-            raise ValueError("TriMesh.barrier_hessian_product: x is an [nv, 3] direction")
+        d = self._direction("barrier_hessian_product", x, "x", "direction")
         starts, entries, nscratch = self._incidence(prox, pt, ee)
         r = BarrierHessianProduct()
         r.pair_terms = torch.empty(nscratch // 12, 4, 3, dtype=torch.float32, device="cuda")
@@ -391,7 +412,7 @@ class TriMesh:
         if lib().zs_rocm_mesh_barrier_hessian_product(*head, 1 if psd else 0, d.data_ptr(), starts.data_ptr(), entries.data_ptr(),
                                                       r.pair_terms.data_ptr(), r.hx.data_ptr(), status.data_ptr()) != 0:
             raise RuntimeError("the barrier Hessian product call failed")
-        r.zero_distance = self._zero_distance(status)
+        r.zero_distance = self._counts(status)
         return r
 
     def friction_lag(self, prox, dhat, kappa, verts=None, mollify=True):
@@ -409,26 +430,19 @@ class TriMesh:
         status = torch.empty(2, dtype=torch.int32, device="cuda")
         if lib().zs_rocm_mesh_friction_lag(*head, r.record.data_ptr(), status.data_ptr()) != 0:
             raise RuntimeError("the friction lag call failed")
-        r.zero_distance = self._zero_distance(status)
+        r.zero_distance = self._counts(status)
         return r
 
     def _friction_args(self, who, lag, u, mu, eps_v):
         """what friction and friction_hessian_product (who, for the messages) share: the arguments checked; returns the displacement, the
         contiguous lists and the head of the C call up to the pair lists"""
-        mu, eps_v = float(mu), float(eps_v)
-        if not (0 <= mu <= float(np.finfo(np.float32).max)):
+        mu, eps_v = float(mu), _positive_f32(who, "eps_v", eps_v)
+        if not (0 <= mu <= FLT_MAX):
             raise ValueError("TriMesh.%s: mu must be finite and not negative" % who)
-        if not (np.isfinite(eps_v) and eps_v > 0 and np.float32(eps_v) > 0 and np.isfinite(np.float32(eps_v))):
-            raise ValueError("TriMesh.%s: eps_v must be finite and positive" % who)
         if not isinstance(lag, FrictionLag):
             raise ValueError("TriMesh.%s: lag is the result of TriMesh.friction_lag" % who)
-        d = _dev_f32(u, 3)
-        if d.shape[0] != self.nv:
-            raise ValueError("TriMesh.%s: u is an [nv, 3] displacement" % who)
-        prox = lag.prox
-        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
-        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
-        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+        d = self._direction(who, u, "u", "displacement")
+        pt, ee, npt, nee = _pair_lists(lag.prox)
         rec = lag.record
         if (npt, nee) != (lag.npt, lag.nee) or tuple(rec.shape) != (npt + nee, 8) or rec.dtype != d.dtype or not rec.is_contiguous():
             raise ValueError("TriMesh.%s: the lists of lag.prox have changed since friction_lag" % who)
@@ -439,27 +453,11 @@ class TriMesh:
         mu lam f0(|ut|) summed over the pairs of lag (a FrictionLag of this mesh), ut the tangential part of the pair's relative
         displacement, and its gradient: a Friction.  eps_v: the static-friction threshold in displacement units (the velocity threshold
         times the time step); below it f0 is the smooth cubic, above it |ut|.  Two calls give the same bytes."""
-        import torch
         d, pt, ee, npt, nee, mu, eps_v = self._friction_args("friction", lag, u, mu, eps_v)
         r = Friction()
-        r.energy = torch.empty((), dtype=torch.float64, device="cuda")
-        r.pt_energy = None if pt is None else torch.empty(npt, dtype=torch.float32, device="cuda")
-        r.ee_energy = None if ee is None else torch.empty(nee, dtype=torch.float32, device="cuda")
-        r.grad = None
-        status = torch.empty(2, dtype=torch.int32, device="cuda")
         head = (self.pol.handle, self._h, d.data_ptr(), _ptr(pt), npt, _ptr(ee), nee, lag.record.data_ptr(), mu, eps_v)
-        tail = (_ptr(r.pt_energy), _ptr(r.ee_energy), r.energy.data_ptr())
-        if gradient:
-            starts, entries, nscratch = self._incidence(lag.prox, pt, ee)
-            scratch = torch.empty(nscratch, dtype=torch.float32, device="cuda")
-            r.grad = torch.empty(self.nv, 3, dtype=torch.float32, device="cuda")
-            rc = lib().zs_rocm_mesh_friction_gradient(*head, starts.data_ptr(), entries.data_ptr(), scratch.data_ptr(), *tail, r.grad.data_ptr(),
-                                                      status.data_ptr())
-        else:
-            rc = lib().zs_rocm_mesh_friction_energy(*head, *tail, status.data_ptr())
-        if rc != 0:
-            raise RuntimeError("the friction call failed")
-        r.overflow = self._zero_distance(status)
+        sides = (("pt_energy", None if pt is None else npt), ("ee_energy", None if ee is None else nee))
+        r.overflow, _ = self._evaluate(r, "friction", head, sides, self._incidence(lag.prox, pt, ee) if gradient else None)
         return r
 
     def friction_hessian_product(self, lag, u, mu, eps_v, x):
@@ -468,9 +466,7 @@ class TriMesh:
         calls give the same bytes."""
         import torch
         d, pt, ee, npt, nee, mu, eps_v = self._friction_args("friction_hessian_product", lag, u, mu, eps_v)
-        xd = _dev_f32(x, 3)
-        if xd.shape[0] != self.nv:
-            raise ValueError("TriMesh.friction_hessian_product: x is an [nv, 3] direction")
+        xd = self._direction("friction_hessian_product", x, "x", "direction")
         starts, entries, nscratch = self._incidence(lag.prox, pt, ee)
         r = FrictionHessianProduct()
         r.pair_terms = torch.empty(nscratch // 12, 4, 3, dtype=torch.float32, device="cuda")
@@ -480,7 +476,7 @@ class TriMesh:
                                                        lag.record.data_ptr(), mu, eps_v, starts.data_ptr(), entries.data_ptr(),
                                                        r.pair_terms.data_ptr(), r.hx.data_ptr(), status.data_ptr()) != 0:
             raise RuntimeError("the friction Hessian product call failed")
-        r.overflow = self._zero_distance(status)
+        r.overflow = self._counts(status)
         return r
 
     def set_rest_shape(self, verts=None):
@@ -488,9 +484,7 @@ class TriMesh:
         of every triangle, the hinges (unique edges with exactly two triangles) with their bending records and the vertex areas.  Returns
         the counts (degenerate triangles, degenerate hinges, non-manifold edges): those elements contribute nothing (a non-manifold edge
         makes no hinge).  A second call recomputes the records on the same hinges.  Leaves set_rest and the contact terms alone."""
-        v = None if verts is None else _dev_f32(verts, 3)
-        if v is not None and v.shape[0] != self.nv:
-            raise ValueError("TriMesh.set_rest_shape: [nv, 3] positions on the same topology")
+        v = self._trial("set_rest_shape", verts)
         if lib().zs_rocm_mesh_set_rest_shape(self.pol.handle, self._h, _ptr(v)) != 0:
             raise RuntimeError("zs_rocm_mesh_set_rest_shape failed")
         self.pol.syncCtx()
@@ -525,9 +519,7 @@ class TriMesh:
                 raise ValueError("TriMesh.%s: %s must be finite and not negative" % (who, name))
         if not getattr(self, "has_rest_shape", False):
             raise ValueError("TriMesh.%s: needs the rest shape, call set_rest_shape first" % who)
-        v = None if verts is None else _dev_f32(verts, 3)
-        if v is not None and v.shape[0] != self.nv:
-            raise ValueError("TriMesh.%s: verts are [nv, 3] positions on the same topology" % who)
+        v = self._trial(who, verts)
         return v, (self.pol.handle, self._h, _ptr(v), mu, lam, kb)
 
     def elastic(self, mu, lam, kb, verts=None, gradient=True):
@@ -537,24 +529,11 @@ class TriMesh:
         k_i x_i|^2 per hinge.  Its domain is cloth: it is zero at rest only where the rest shape is flat across the hinge, and on a curved
         rest shape it penalises the rest curvature too.  verts [nv, 3]: trial positions instead of the mesh's own.  A zero mu and lam (or
         kb) skips the membrane (or bending) kernels.  Two calls give the same bytes."""
-        import torch
         v, head = self._elastic_args("elastic", mu, lam, kb, verts)
-        f32 = dict(dtype=torch.float32, device="cuda")
         r = Elastic()
-        r.energy = torch.empty((), dtype=torch.float64, device="cuda")
-        r.tri_energy, r.hinge_energy = torch.empty(self.nt, **f32), torch.empty(self.num_hinges, **f32)
-        r.grad, r.elem_terms, r.nt = None, None, self.nt
-        status = torch.empty(2, dtype=torch.int32, device="cuda")
-        tail = (r.tri_energy.data_ptr(), r.hinge_energy.data_ptr(), r.energy.data_ptr())
-        if gradient:
-            r.elem_terms = torch.empty(self._elastic_scratch, **f32)
-            r.grad = torch.empty(self.nv, 3, **f32)
-            rc = lib().zs_rocm_mesh_elastic_gradient(*head, r.elem_terms.data_ptr(), *tail, r.grad.data_ptr(), status.data_ptr())
-        else:
-            rc = lib().zs_rocm_mesh_elastic_energy(*head, *tail, status.data_ptr())
-        if rc != 0:
-            raise RuntimeError("the elastic call failed")
-        r.overflow = self._zero_distance(status)
+        r.nt = self.nt
+        sides = (("tri_energy", self.nt), ("hinge_energy", self.num_hinges))
+        r.overflow, r.elem_terms = self._evaluate(r, "elastic", head, sides, (self._elastic_scratch,) if gradient else None)
         return r
 
     def elastic_hessian_product(self, mu, lam, kb, x, verts=None, psd=False):
@@ -565,9 +544,7 @@ class TriMesh:
         calls give the same bytes."""
         import torch
         v, head = self._elastic_args("elastic_hessian_product", mu, lam, kb, verts)
-        d = _dev_f32(x, 3)
-        if d.shape[0] != self.nv:
-            raise ValueError("TriMesh.elastic_hessian_product: x is an [nv, 3] direction")
+        d = self._direction("elastic_hessian_product", x, "x", "direction")
         r = ElasticHessianProduct()
         r.nt = self.nt
         r.elem_terms = torch.empty(self._elastic_scratch, dtype=torch.float32, device="cuda")
@@ -576,14 +553,8 @@ class TriMesh:
         if lib().zs_rocm_mesh_elastic_hessian_product(*head, 1 if psd else 0, d.data_ptr(), r.elem_terms.data_ptr(), r.hx.data_ptr(),
                                                       status.data_ptr()) != 0:
             raise RuntimeError("the elastic Hessian product call failed")
-        r.overflow = self._zero_distance(status)
+        r.overflow = self._counts(status)
         return r
-
-    def _direction(self, who, direction):
-        d = _dev_f32(direction, 3)
-        if d.shape[0] != self.nv:
-            raise ValueError("TriMesh.%s: direction is an [nv, 3] array" % who)
-        return d
 
     def max_step(self, prox, direction, verts=None, slack=0.1, t_max=1.0, max_iter=256):
         """a conservative bound on the step t <= t_max for which verts + t direction (verts=None: the mesh's own positions) keeps every
@@ -591,22 +562,16 @@ class TriMesh:
         keeps its distance above slack x its distance at t = 0; max_iter caps the distance evaluations of one pair.  Only the pairs of
         prox are looked at: step_candidates gives a list that is complete for a direction.  Two calls give the same bytes."""
         import torch
-        slack, t_max = float(slack), float(t_max)
+        slack, t_max = float(slack), _positive_f32("max_step", "t_max", t_max)
         if not (0.0 < slack < 1.0 and 0.0 < float(np.float32(slack)) < 1.0):
             raise ValueError("TriMesh.max_step: slack must be inside (0, 1)")
-        if not (np.isfinite(t_max) and t_max > 0 and np.float32(t_max) > 0 and np.isfinite(np.float32(t_max))):
-            raise ValueError("TriMesh.max_step: t_max must be finite and positive")
         if int(max_iter) != max_iter or max_iter < 1 or max_iter > 2 ** 31 - 1:
             raise ValueError("TriMesh.max_step: max_iter is an integer of at least 1")
         if not isinstance(prox, Proximity):
             raise ValueError("TriMesh.max_step: prox is the result of TriMesh.proximity or TriMesh.step_candidates")
         d = self._direction("max_step", direction)
-        v = None if verts is None else _dev_f32(verts, 3)
-        if v is not None and v.shape[0] != self.nv:
-            raise ValueError("TriMesh.max_step: verts are [nv, 3] positions on the same topology")
-        pt = None if prox.pt_pairs is None else prox.pt_pairs.contiguous()
-        ee = None if prox.ee_pairs is None else prox.ee_pairs.contiguous()
-        npt, nee = (0 if pt is None else len(pt)), (0 if ee is None else len(ee))
+        v = self._trial("max_step", verts)
+        pt, ee, npt, nee = _pair_lists(prox)
         r = StepBound()
         r.t = torch.empty((), dtype=torch.float32, device="cuda")
         r.pt_toi = None if pt is None else torch.empty(npt, dtype=torch.float32, device="cuda")
@@ -615,9 +580,8 @@ class TriMesh:
         if lib().zs_rocm_mesh_ccd(self.pol.handle, self._h, _ptr(v), d.data_ptr(), _ptr(pt), npt, _ptr(ee), nee, slack, t_max, int(max_iter),
                                   _ptr(r.pt_toi), _ptr(r.ee_toi), r.t.data_ptr(), status.data_ptr()) != 0:
             raise RuntimeError("the CCD call failed")
-        self.pol.syncCtx()
-        s = status.tolist()
-        r.zero_distance, r.capped = (int(s[0]), int(s[1])), (int(s[2]), int(s[3]))
+        s = self._counts(status)
+        r.zero_distance, r.capped = s[:2], s[2:]
         return r
 
     def step_candidates(self, direction, t_max=1.0, margin=None):
