@@ -1150,7 +1150,7 @@ ZS_ROCM_EXPORT int zs_rocm_dist_halo_plan_exchange(zs_rocm_halo_plan *, zs_rocm_
 ZS_ROCM_EXPORT zs_rocm_halo_plan *zs_rocm_dist_halo_plan_from_lists(zs_rocm_dist *, int side, int npeers, const int *peerRank,
                                                                     const size_t *peerOffset, const size_t *peerCount, const int *blocks,
                                                                     size_t total);
-/* One sub-step of the slotted MPM path in ONE call (zpc_amd/csrc/dist.hip): gridB := 0; fused G2P (gridA) + P2G (gridB) over the boundary
+/* One sub-step of the slotted MPM path in ONE call (zpc_amd/csrc/dist.hip): gridB := 0 (unless gridBIsClear, below); fused G2P (gridA) + P2G (gridB) over the boundary
  * blocks [0, nBoundary), then the interior blocks (+ re-home / commit); the ghost-block exchange of the plan on commPolicy's stream behind
  * the boundary range, overlapping the interior (rangeSchedule: as two launches, or as one whose boundary workgroups count themselves off);
  * grid update of gridB (extf, maxVelSqr) [+ collider]; allreduce(max) of maxVelSqr.  Nothing
@@ -1206,6 +1206,14 @@ typedef struct zs_rocm_mpm_step {
                                             exchange buffer (zs_rocm_mpm_halo_pack, chn0 = 0, nchn = 1) on commPolicy's stream at the moment the exchange starts.  Only the
                                             boundary blocks write those nodes, so it must equal the same pack taken after the step: the check that the hand-over of a
                                             schedule lets the exchange see complete sums (tests/test_dist_gpu.py) */
+  float *gridClear;                      /* NULL, or (8^3 blocks; ignored for 4^3) a THIRD grid of the same partition, 16-byte aligned, neither gridA nor
+                                            gridB (else -1): the fused block kernel writes zero over it, every workgroup its own block, every block of
+                                            [0, nblocks) once per step whatever the range schedule.  Rotate three grids -- gather from A, scatter into B,
+                                            clear C; next step gather from B, scatter into C, clear A -- and the grid that becomes the target has been
+                                            cleared by the step before */
+  int gridBIsClear;                      /* non-zero: gridB is all zero already (the previous step's gridClear, same partition, nothing written to it
+                                            since), the call skips its memset of gridB.  Honoured only with gridClear != NULL and 8^3 blocks; in every
+                                            other case gridB is cleared here as before.  Say 0 after anything that re-partitions or writes the grids */
   const zs_rocm_levelset *levelset;      /* NULL, or the boundary is this level set with `collider`'s type and motion (zs_rocm_mpm_apply_boundary_levelset);
                                             a level set without a collider is refused (-1) before anything runs */
 } zs_rocm_mpm_step;

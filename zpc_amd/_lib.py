@@ -71,7 +71,7 @@ class MpmStep(C.Structure):
                 ("maxVelSqr", C.c_void_p), ("collider", C.c_void_p), ("nBoundary", C.c_size_t), ("dist", C.c_void_p),
                 ("plan", C.c_void_p), ("commPolicy", C.c_void_p), ("haloGrid", C.c_void_p), ("evTransferBegin", C.c_void_p),
                 ("evTransferEnd", C.c_void_p), ("evBreakdown", C.POINTER(C.c_void_p)), ("haloChannels", C.c_int), ("rangeSchedule", C.c_int), ("handoverSnapshot", C.c_void_p),
-                ("levelset", C.c_void_p)]
+                ("gridClear", C.c_void_p), ("gridBIsClear", C.c_int), ("levelset", C.c_void_p)]
 
 
 class MpmParams(C.Structure):

@@ -414,7 +414,8 @@ extern "C" {
 // The whole sub-step of the slotted MPM path behind ONE C-ABI call: no host code of the caller runs between the kernels, so a C++ host
 //  and bench.py enqueue a step for the price of one call -- at 8 ranks a rank's step is ~1 ms and a Python loop of ~8
 // ctypes / RCCL calls per step is first-order.  Enqueued, in order, on the policy's stream:
-//   gridB := 0;  fused G2P (from gridA) + P2G (into gridB) of the blocks [0, nBoundary)   [boundary blocks: the partition is numbered with
+//   gridB := 0 (skipped when the caller rotates three grids and the previous step's block kernel cleared this one: gridClear / gridBIsClear);
+//   fused G2P (from gridA) + P2G (into gridB) of the blocks [0, nBoundary)   [boundary blocks: the partition is numbered with
 //   them first];  event;  the same for [nBoundary, nblocks) + re-home + commit;  wait for the exchange;  grid update of gridB (+ extf dt,
 //   max |v|^2 into maxVelSqr);  allreduce(max) of maxVelSqr over the ranks (CFL).
 // and on commPolicy's stream (a second stream), behind the event: pack -> grouped ncclSend / ncclRecv -> atomic unpack-add of the ghost
@@ -432,12 +433,22 @@ int zs_rocm_mpm_step_slotted(zs_rocm_policy *pol, const zs_rocm_mpm_step *a) {
   if (!nb) return 0;
   const int side = a->params->side;
   const size_t gridBytes = nb * (size_t)7 * side * side * side * sizeof(float);
-  zs_rocm_memset(pol, a->gridB, 0, gridBytes);
-  float *const hgrid = a->haloGrid ? a->haloGrid : a->gridB;
-  const bool exchange = a->dist && a->plan && a->plan->total;
   if (a->haloChannels < 0 || a->haloChannels > 7) return -1;
   if (a->rangeSchedule < ZS_ROCM_RANGES_IN_TURN || a->rangeSchedule > ZS_ROCM_RANGES_ONE_LAUNCH) return -1;
   if (a->rangeSchedule == ZS_ROCM_RANGES_ONE_LAUNCH && side != 8) return -1;   // (the 4^3-block kernel does not count its workgroups off)
+  // Three-grid rotation (8^3 blocks): the block kernel writes zero over gridClear, one block per workgroup, every block of [0, nblocks) once
+  // per step whatever the range schedule -- the target of the NEXT step, whose caller then says gridBIsClear and saves the memset.  The 4^3
+  // kernel does not clear: side 4 ignores both fields.
+  float *const gridClear = side == 8 ? a->gridClear : nullptr;
+  if (gridClear && (gridClear == a->gridA || gridClear == a->gridB || ((uintptr_t)gridClear & 15u))) return -1;
+  if (!(gridClear && a->gridBIsClear)) zs_rocm_memset(pol, a->gridB, 0, gridBytes);
+  float *const hgrid = a->haloGrid ? a->haloGrid : a->gridB;
+  const bool exchange = a->dist && a->plan && a->plan->total;
+  // one range of the transfer; the commit kernel of the finish pass also zeroes maxVelSqr for the grid update behind it (same stream)
+  auto slots = [&](zs_rocm_policy *on, size_t b0, size_t b1, int finish, unsigned long long *signal, size_t signalBlocks) {
+    return mpm_g2p2g_slots_signal(on, a->params, a->particles, a->table, a->gridA, a->gridB, nb, a->storage, a->writeAll, b0, b1, finish, signal,
+                                  signalBlocks, gridClear, finish ? a->maxVelSqr : nullptr);
+  };
   const int hch = a->haloChannels ? a->haloChannels : 7;
   const bool overlap = exchange && a->commPolicy && a->nBoundary > 0 && a->nBoundary < nb;
   int rc = 0;
@@ -480,7 +491,7 @@ int zs_rocm_mpm_step_slotted(zs_rocm_policy *pol, const zs_rocm_mpm_step *a) {
         ZSR_CHECK(hipStreamSynchronize(L.stream));   // once per plan: the gate on the OTHER stream must never read the word before it is zero
         p->signalTarget = 0;
       }
-      rc = mpm_g2p2g_slots_signal(pol, a->params, a->particles, a->table, a->gridA, a->gridB, nb, a->storage, a->writeAll, 0, nb, 1, p->signal, a->nBoundary);
+      rc = slots(pol, 0, nb, 1, p->signal, a->nBoundary);
       if (rc) return rc;  // (bad arguments fail before any launch: nothing has been counted)
       p->signalTarget += a->nBoundary;
       {
@@ -507,7 +518,7 @@ int zs_rocm_mpm_step_slotted(zs_rocm_policy *pol, const zs_rocm_mpm_step *a) {
         Launch C(a->commPolicy, "step: boundary range start");
         ZSR_CHECK(hipStreamWaitEvent(C.stream, p->evReady, 0));
       }
-      rc = zs_rocm_mpm_g2p2g_slots(bpol, a->params, a->particles, a->table, a->gridA, a->gridB, nb, a->storage, a->writeAll, 0, a->nBoundary, 0);
+      rc = slots(bpol, 0, a->nBoundary, 0, nullptr, 0);
       if (rc) return rc;  // (nothing of the step has been committed: the range ran with finish = 0 and bad arguments fail before any launch)
       bd(1, bpol);
       {
@@ -531,14 +542,14 @@ int zs_rocm_mpm_step_slotted(zs_rocm_policy *pol, const zs_rocm_mpm_step *a) {
     // the second range ALWAYS runs, with its finish pass (re-home + commit): a failed exchange must not leave outbox records, claim words
     // and mover counts of the boundary range uncommitted -- the slot storage stays consistent, the error is returned afterwards
     if (sched == ZS_ROCM_RANGES_IN_TURN) {
-      rc = zs_rocm_mpm_g2p2g_slots(pol, a->params, a->particles, a->table, a->gridA, a->gridB, nb, a->storage, a->writeAll, a->nBoundary, nb, 1);
+      rc = slots(pol, a->nBoundary, nb, 1, nullptr, 0);
     } else if (sched == ZS_ROCM_RANGES_SIDE_BY_SIDE) {  // the interior range next to the boundary range; the finish pass needs the outbox records of both
-      rc = zs_rocm_mpm_g2p2g_slots(pol, a->params, a->particles, a->table, a->gridA, a->gridB, nb, a->storage, a->writeAll, a->nBoundary, nb, 0);
+      rc = slots(pol, a->nBoundary, nb, 0, nullptr, 0);
       {
         Launch L(pol, "step: wait for the boundary range");
         ZSR_CHECK(hipStreamWaitEvent(L.stream, p->evBoundary, 0));
       }
-      const int rcf = zs_rocm_mpm_g2p2g_slots(pol, a->params, a->particles, a->table, a->gridA, a->gridB, nb, a->storage, a->writeAll, nb, nb, 1);
+      const int rcf = slots(pol, nb, nb, 1, nullptr, 0);   // (finish only: launches no block, clears nothing)
       if (!rc) rc = rcf;
     }
     bd(2, pol);
@@ -551,7 +562,7 @@ int zs_rocm_mpm_step_slotted(zs_rocm_policy *pol, const zs_rocm_mpm_step *a) {
     if (rcx || rc) return rcx ? rcx : rc;
   } else {
     bd(1, pol);
-    rc = zs_rocm_mpm_g2p2g_slots(pol, a->params, a->particles, a->table, a->gridA, a->gridB, nb, a->storage, a->writeAll, 0, nb, 1);
+    rc = slots(pol, 0, nb, 1, nullptr, 0);
     if (rc) return rc;
     bd(2, pol);
     stamp(a->evTransferEnd);
@@ -563,7 +574,7 @@ int zs_rocm_mpm_step_slotted(zs_rocm_policy *pol, const zs_rocm_mpm_step *a) {
     bd(4, pol);
     bd(5, pol);
   }
-  if (a->maxVelSqr) zs_rocm_memset(pol, a->maxVelSqr, 0, sizeof(float));
+  // (maxVelSqr is zero: every path above has run the finish pass on this stream, whose commit kernel zeroes the word -- a failed range returns)
   zs_rocm_mpm_grid_update(pol, a->params, a->gridB, nb, a->extf, a->maxVelSqr);
   if (a->levelset) rc = zs_rocm_mpm_apply_boundary_levelset(pol, a->params, a->table, a->gridB, nb, a->collider, a->levelset);
   else if (a->collider) zs_rocm_mpm_apply_boundary(pol, a->params, a->table, a->gridB, nb, a->collider);

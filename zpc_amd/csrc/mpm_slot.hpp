@@ -34,6 +34,9 @@ struct SlotArgs {
   const unsigned char *blockEdge;  // [nblocks] or NULL: 1 = a block of {-1..2}^3 around this one is not in the partition (zs_rocm_mpm_partition_edge)
   unsigned long long *signal;      // NULL, or a running count: every workgroup of the blocks [0, signalBlocks) adds 1 when its grid sums are in L2
   int signalBlocks;                // (8^3 blocks only: the multi-GPU step's exchange stream starts behind the boundary blocks of ONE launch, dist.hip)
+  float *gridClear;                // NULL, or (8^3 blocks only) a third grid of the same partition that neither this step's gather nor its scatter
+                                   // touches: every launched workgroup writes zero over ITS block of it -- the next step's target, cleared
+                                   // without a memset (zs_rocm_mpm_step::gridClear, dist.hip)
 };
 
 constexpr int SL_NCTR = 256, SL_SENT = 8, SL_DELIVERED = 8 + SL_NCTR;  // layout of the status words (zs_rocm.h: ZS_ROCM_SLOT_STATUS_WORDS)

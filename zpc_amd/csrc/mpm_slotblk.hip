@@ -31,6 +31,9 @@
 //     faces of the shell a list entry of the bin has reached (a 6-bit mask kept while the lists are scattered; none at rest).  Every LDS
 //     read of a pass is issued before the first is used, and a pass writes zero over what it read: the arena is cleared once per
 //     workgroup, never per bin (blk_flush_nodes and the bin end of blk_consumer; profiles/block_flush.md).
+//   * the step call's grid reset rides here: with SlotArgs::gridClear set, every workgroup writes zero over its own block of a third grid,
+//     the NEXT step's target, as the last thing it does (blk_clear_block; an empty block at its early exit) -- three grids rotate and no
+//     memset stands in front of the step's first workgroup (dist.hip, profiles/grid_rotation.md).
 // The per-particle code (slot_produce_entry), the consumers' accumulation (g2p2g_consume_set), the mover protocol, slot_rehome_kernel
 // and slot_commit_kernel are those of mpm_slotted.hip; results differ only in summation order.
 #include "mpm_slot.hpp"
@@ -451,6 +454,18 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
   __syncthreads();  // the last bin is flushed
 }
 
+// The workgroup's own block of the grid that rotates in as the NEXT step's target (A.gridClear; NULL: the caller clears with a memset):
+// 7 x 512 floats = 896 plain 16-byte stores over the 512 threads, fire and forget.  The grid is neither gathered from nor scattered into in
+// this step and block `blk` of it belongs to this workgroup alone, so the kernel boundary is all the ordering there is.
+// blockClear = the block's first float (NULL: nothing to clear).
+__device__ __forceinline__ void blk_clear_block(float *blockClear, int tid) {
+  if (!blockClear) return;
+  float4 *const p = reinterpret_cast<float4 *>(blockClear);
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  p[tid] = z;
+  if (tid < 7 * 512 / 4 - 512) p[512 + tid] = z;
+}
+
 template <int SMODEL, bool WRITE_ALL>
 static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp, ParticlesDev ps, BhtDev t, SlotArgs A) {
   constexpr int NC = 512;
@@ -465,11 +480,12 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   __shared__ unsigned s_xCnt[3], s_xq[3][SL_XQ];
   __shared__ int s_nbrBlk[27], s_nbrBin[2][27], s_nbr8[8];
   __shared__ int s_cnt[2][4];
-  __shared__ int s_total[8], s_gbase[8], s_nch[8], s_binQ[8], s_oc[8];
+  __shared__ int s_total[8], s_gbase[8], s_binQ[8], s_oc[8];
   __shared__ unsigned char s_chBin[SB_MAXCH], s_chIdx[SB_MAXCH];
   __shared__ unsigned s_desc[SB_MAXCH + 5];
   __shared__ unsigned s_done;
   __shared__ int s_sums[3], s_G;
+  __shared__ float *s_clear;  // this block of A.gridClear (NULL: none), parked here from the head to the tail of the kernel
   const BlkShared sh{s_varena, s_parena, s_stage, s_smask, s_tab, s_masks, s_clr, s_arrLocal, s_arrCnt, s_arrQ, s_xCnt, s_xq, s_nbrBlk, s_nbrBin, s_nbr8,
                      s_cnt, s_oc, s_desc, &s_done, s_sums};
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -492,7 +508,10 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
     s_sums[tid] = 0;
   }
   if (tid < 8) (&s_cnt[0][0])[tid] = 0;
-  if (tid == 0) s_done = 0u;
+  if (tid == 0) {
+    s_done = 0u;
+    s_clear = A.gridClear ? A.gridClear + (size_t)blk * 7 * NC : nullptr;
+  }
   if (tid >= 64 && tid < 64 + 27) s_nbrBlk[tid - 64] = A.nbr27[(size_t)blk * 27 + (tid - 64)];
   if (tid >= 96 && tid < 104) s_nbr8[tid - 96] = A.nbr[(size_t)blk * 8 + (tid - 96)];
   int borg[3];
@@ -504,13 +523,13 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
     // sums, so it reports to the one-launch schedule's counter at once
     if (tid < 8) A.moverCount[bin0 + tid] = 0;
     if (A.signal && blk < A.signalBlocks && tid == 0) atomicAdd(A.signal, 1ull);
+    blk_clear_block(s_clear, tid);
     return;
   }
   if (tid == 0) {  // the block's chunk sequence
     int G = 0, q = 0;
     for (int b = 0; b < 8; ++b) {
       const int nch = (s_total[b] + 255) >> 8;
-      s_nch[b] = nch;
       s_gbase[b] = G;
       s_binQ[b] = q;
       s_oc[b] = 0;
@@ -597,6 +616,10 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
     __syncthreads();   // ... and every wave's
     if (tid == 0) atomicAdd(A.signal, 1ull);
   }
+  // last of all (behind the role functions' last barrier, nothing of the chunk loop alive, and behind the signal, whose vmcnt(0) must not
+  // wait for these stores).  The address comes back from LDS, on this path and at the early exit: with A.gridClear read at the early exit
+  // every instantiation spilled two more SGPRs across the chunk loop and NACC's a VGPR as well (8 B of private segment).
+  blk_clear_block(s_clear, tid);
 }
 
 template <int M, bool WA> static void launch_blk(hipStream_t stream, unsigned nblk, const MpmDev &mp, const ParticlesDev &pd, const BhtDev &t, const SlotArgs &A) {

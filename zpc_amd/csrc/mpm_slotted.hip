@@ -290,8 +290,11 @@ static __global__ __launch_bounds__(256) void slot_rehome_kernel(ParticlesDev ps
 
 // after the step: departures leave the occupancy words, this step's arrivals enter them (the lowest free rounds: in-bin arrivals first,
 // then the arrivals from other bins), the counters are zero again
-static __global__ __launch_bounds__(256) void slot_commit_kernel(unsigned *cellMask, unsigned *claim, size_t ncells, int K) {
+// zeroWord (NULL: none): one float set to zero by thread 0 -- the step call's maxVelSqr, which the grid update behind this kernel on the same
+// stream accumulates into (a launch of its own as a 4-byte memset)
+static __global__ __launch_bounds__(256) void slot_commit_kernel(unsigned *cellMask, unsigned *claim, size_t ncells, int K, float *zeroWord) {
   const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c == 0 && zeroWord) *zeroWord = 0.f;
   if (c >= ncells) return;
   const unsigned tk = claim[c], clr = claim[ncells + c];
   if (!tk && !clr) return;
@@ -444,17 +447,22 @@ size_t zs_rocm_mpm_slot_list(zs_rocm_policy *pol, const unsigned *cellMask, size
 int zs_rocm_mpm_g2p2g_slots(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab,
                             const float *gridA, float *gridB, size_t nblocks, const zs_rocm_slot_storage *st, int writeAll,
                             size_t blockBegin, size_t blockEnd, int finish) {
-  return zsr::mpm_g2p2g_slots_signal(pol, p, ps, tab, gridA, gridB, nblocks, st, writeAll, blockBegin, blockEnd, finish, nullptr, 0);
+  return zsr::mpm_g2p2g_slots_signal(pol, p, ps, tab, gridA, gridB, nblocks, st, writeAll, blockBegin, blockEnd, finish, nullptr, 0, nullptr, nullptr);
 }
 }  // extern "C"
 namespace zsr {
 // ... and with `signal`: every workgroup of the blocks [0, signalBlocks) of the range adds 1 to *signal when its sums have reached grid B
-// (8^3 blocks only; zs_rocm_mpm_step_slotted's one-launch schedule waits for the count on its exchange stream)
+// (8^3 blocks only; zs_rocm_mpm_step_slotted's one-launch schedule waits for the count on its exchange stream).
+// gridClear (NULL: none; 8^3 blocks only, ignored by the 4^3 kernel): a third grid of the partition, 16-byte aligned, that is neither gridA
+// nor gridB: every workgroup of the range writes zero over its own block of it (a range [nb, nb) launches nothing and clears nothing).
+// zeroWord (NULL: none): a float the finish pass's commit kernel sets to zero (the step call's maxVelSqr).
 int mpm_g2p2g_slots_signal(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_rocm_particles ps, const zs_rocm_bht_3 *tab, const float *gridA,
                            float *gridB, size_t nblocks, const zs_rocm_slot_storage *st, int writeAll, size_t blockBegin, size_t blockEnd, int finish,
-                           unsigned long long *signal, size_t signalBlocks) {
+                           unsigned long long *signal, size_t signalBlocks, float *gridClear, float *zeroWord) {
   if (!st) return -1;
   if (signal && p->side != 8) return -1;
+  if (p->side != 8) gridClear = nullptr;
+  if (gridClear && (gridClear == gridA || gridClear == gridB || ((uintptr_t)gridClear & 15u))) return -1;
   unsigned *const cellMask = st->cellMask;
   const int K = st->K, outboxCap = st->outboxCap;
   const int *const nbr = st->nbr, *const nbr27 = st->nbr27;
@@ -477,7 +485,7 @@ int mpm_g2p2g_slots_signal(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_
   const unsigned nbinsAll = (unsigned)(nblocks * bpb);
   const unsigned nbins = blockBegin < blockEnd ? (unsigned)((blockEnd - blockBegin) * bpb) : 0u;
   const SlotArgs A{gridA, gridB, cellMask, K, nbr, nbr27, moverCount, claim, moverRec, status, (int)(blockBegin * bpb), (int)nbins, (int)nbinsAll, outboxCap,
-                   st->blockEdge, signal, (int)signalBlocks};
+                   st->blockEdge, signal, (int)signalBlocks, gridClear};
 #define CALL_REHOME3(M, WA)                                                                                                              \
   hipLaunchKernelGGL((slot_rehome_kernel<model_is_fluid(M), model_uses_logjp(M), WA>), dim3(ceil_div((size_t)nbinsAll, 32)), dim3(256), 0,  \
                      L.stream, pd, (const unsigned *)cellMask, claim, (const int *)moverCount, (const float *)moverRec, outboxCap,        \
@@ -501,7 +509,7 @@ int mpm_g2p2g_slots_signal(zs_rocm_policy *pol, const zs_rocm_mpm_params *p, zs_
   if (finish) ZSR_DISPATCH_PURE_(0, p->model, CALL_REHOME)
   if (finish) {
     const size_t ncells = (size_t)nbinsAll * 64;
-    hipLaunchKernelGGL(slot_commit_kernel, dim3(ceil_div(ncells, 256)), dim3(256), 0, L.stream, cellMask, claim, ncells, K);
+    hipLaunchKernelGGL(slot_commit_kernel, dim3(ceil_div(ncells, 256)), dim3(256), 0, L.stream, cellMask, claim, ncells, K, zeroWord);
   }
   return 0;
 }

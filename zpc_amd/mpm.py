@@ -57,6 +57,12 @@ class MpmTransfer:
                                 bulk, viscosity)
         self.table = None
         self.grid = None
+        # slotted storage with 8^3 blocks rotates THREE grids through step_slotted(): gathered from (self.grid), scattered into (self.grid2),
+        # cleared by the block kernel for the step after (self.grid3).  _clean_grid = (tensor, table) while that tensor is known to be all zero
+        # under that partition: set by step_slotted() alone, dropped by everything else that writes a grid or changes the partition
+        self.grid2 = self.grid3 = None
+        self._clean_grid = None
+        self.rotate_grids = True   # False: step_slotted() passes no gridClear -- two grids, a memset per step (what 4^3 blocks always do)
         self.nblocks = 0
         self.order = self.bin_start = self.cell_count = self.nbr = None
         self.binned = False
@@ -66,6 +72,11 @@ class MpmTransfer:
         # run-level record of the slotted storage's status words: folded in by check_slots() (which unslot() calls), so that a
         # re-partition (slot() starts a fresh status buffer) can never discard a latched flag or a lost-mover count
         self.slot_record = {"sent": 0, "homed": 0, "flags": [0] * 5, "periods": 0, "edge_periods": 0, "log": []}
+
+    def _grids_written(self):
+        """a grid was written outside step_slotted(), or the partition changed: no buffer counts as cleared by the last step any more (the
+        next step_slotted() clears its target with a memset)"""
+        self._clean_grid = None
 
     def _zero(self, t):
         """clear device memory ON THE POLICY'S STREAM (torch's zero_() would run on torch's current stream, which is ordered with
@@ -172,6 +183,7 @@ class MpmTransfer:
         self.block_order, self.block_axes = order, (tuple(axes) if axes is not None else None)
         self.nblocks = self.table.size()
         self.slotted = False
+        self._grids_written()
         nc = self.side ** 3
         self.grid = torch.zeros(self.nblocks * 7 * nc, dtype=torch.float32, device=self.device)
         self.nbr = torch.empty(self.nblocks * 8, dtype=torch.int32, device=self.device)
@@ -186,6 +198,7 @@ class MpmTransfer:
         self.table = Bht(3, int(nblocks))
         self.table.assign(self.pol, active_keys_ptr, int(nblocks))
         self.nblocks = int(nblocks)
+        self._grids_written()
         nc = self.side ** 3
         self.grid = torch.zeros(self.nblocks * 7 * nc, dtype=torch.float32, device=self.device)
         self.nbr = torch.empty(self.nblocks * 8, dtype=torch.int32, device=self.device)
@@ -233,6 +246,9 @@ class MpmTransfer:
         fused step keeps valid by itself while particles move (no re-bins).  Needs the partition; lane width 64."""
         assert self.L == 64 and not self.aos and self.table is not None and not self.slotted
         L = lib()
+        self._grids_written()
+        # the third grid of step_slotted()'s rotation (8^3 blocks): allocated here, outside any timed region
+        self.grid3 = torch.empty_like(self.grid) if self.side == 8 else None
         self.K = int(K)
         self.outbox_cap = int(outbox_cap)   # movers one bin can send per step (a bin holds 512 particles at 8 per cell)
         self.nbins = self.nblocks * (self.side // 4) ** 3
@@ -286,6 +302,11 @@ class MpmTransfer:
         pool = self.__dict__.setdefault("_pool", {})
         if "slots_alt" not in pool or pool["slots_alt"].numel() < n:
             pool["slots_alt"] = torch.empty(n, dtype=torch.float32, device=self.device)
+        if self.side == 8:   # the third grid of step_slotted()'s rotation, for either parity of the re-partitions
+            g = int(self.grid.numel() * growth) + 64
+            for name in ("gridC0", "gridC1"):
+                if name not in pool or pool[name].numel() < g:
+                    pool[name] = torch.empty(g, dtype=torch.float32, device=self.device)
         self.pol.syncCtx()
 
     def repartition_slotted(self, margin=None, strict=True):
@@ -346,6 +367,8 @@ class MpmTransfer:
         self.table, self.nblocks, self.nbins, self.n_slots = new_table, nb, nbins, nbins * self.K * 64
         self.buf, self.cell_mask, self.grid = sbuf, mask, grid
         self.grid2 = self._backing("gridB%d" % flip, nb * 7 * nc, torch.float32, zero=True)
+        self.grid3 = self._backing("gridC%d" % flip, nb * 7 * nc, torch.float32) if self.side == 8 else None
+        self._grids_written()   # (new partition: the next step_slotted() clears its target itself)
         self.nbr = self._backing("nbr", nb * 8, torch.int32, spare=True)
         L.zs_rocm_mpm_build_neighbors(self.pol.handle, self.table.handle, self.nbr.data_ptr(), self.kstride)
         self.nbr27 = self._backing("nbr27", nb * 27, torch.int32, spare=True)
@@ -447,9 +470,11 @@ class MpmTransfer:
 
     # ------------------------------------------------------------------ one sub-step
     def clear_grid(self):
+        self._grids_written()
         self._zero(self.grid)  # TileVector::reset(pol, 0) (TileVector.hpp:636-640)
 
     def p2g(self, binned=None):
+        self._grids_written()
         binned = self.binned if binned is None else binned
         bs = self.bin_start.data_ptr() if binned else None
         cc = self.cell_count.data_ptr() if binned else None
@@ -458,6 +483,7 @@ class MpmTransfer:
                               self.nblocks, bs, cc, nb)
 
     def grid_update(self, extf=(0.0, 0.0, 0.0), max_vel=None):
+        self._grids_written()
         e = (C.c_float * 3)(*extf)
         lib().zs_rocm_mpm_grid_update(self.pol.handle, C.byref(self.params), self.grid.data_ptr(), self.nblocks, e,
                                       max_vel.data_ptr() if max_vel is not None else None)
@@ -466,6 +492,7 @@ class MpmTransfer:
         """ApplyBoundaryConditionOnGridBlocks (simulation/grid/GridOp.hpp:111-164): collider.resolveCollision on every grid node
         with mass; call after grid_update.  `collider`: make_collider(...); with levelset= (a SparseLevelSet or its .view):
         make_levelset_collider(...), the level set is the shape."""
+        self._grids_written()
         tr = _transition_view(levelset)
         if tr is not None:
             if lib().zs_rocm_mpm_apply_boundary_transition(self.pol.handle, C.byref(self.params), self.table.handle, self.grid.data_ptr(),
@@ -599,6 +626,7 @@ class MpmTransfer:
 
     def p2c2g(self, kind=0):
         """kind 0 P2C2GTransfer, 1 P2C2GTransferMomentum, 2 P2C2GTransferForce; ADDS into grid channels m, mv."""
+        self._grids_written()
         if lib().zs_rocm_mpm_p2c2g(self.pol.handle, C.byref(self.params), self.particles(), self.buckets._h, self.table.handle,
                                    self.grid.data_ptr(), self.nblocks, int(kind)) != 0:
             raise RuntimeError("zs_rocm_mpm_p2c2g refused its arguments")
@@ -628,6 +656,7 @@ class MpmTransfer:
         reorder=True: the particles are binned anew by their current positions (count / scan / distribute only) and the step
         itself carries them into that order -- inputs read from the old buffer through the permutation, results stored to the
         other buffer (zs_rocm_mpm_g2p2g_reorder_range): a re-bin without the separate reorder pass."""
+        self._grids_written()   # (this path clears its target itself and swaps two of the grids)
         if self.slotted:
             if reorder:
                 raise ValueError("slotted storage: no re-ordering steps (the step keeps the order itself)")
@@ -692,6 +721,10 @@ class MpmTransfer:
         """One whole sub-step on slotted storage behind ONE C-ABI call (zs_rocm_mpm_step_slotted): second grid := 0, fused G2P2G over the
         boundary blocks [0, n_boundary) then the interior, ghost-block exchange of `plan` on comm_pol's stream overlapping the interior,
         grid update (+ collider), CFL allreduce(max) of max_vel.  The grids swap: self.grid is the new one afterwards.
+        8^3 blocks rotate three grids: the block kernel clears self.grid3 while it gathers from self.grid and scatters into self.grid2, and
+        the call skips its memset whenever its target is the buffer the previous step_slotted() cleared under the same partition and nothing
+        else has written a grid since (_clean_grid; build_partition, reorder_partition, repartition_slotted, slot, clear_grid, p2g, g2p2g,
+        grid_update, apply_boundary all drop it).  Write self.grid2 / self.grid3 from outside only through those, or call _grids_written().
         comm: NativeComm, plan: NativeHaloPlan (both None on a single rank).  levelset=: the boundary is that level set with `collider`'s
         (make_levelset_collider) type and motion.  A LevelSetSequence (or its view()) as levelset= is served by two calls on the policy's
         stream: this step without a collider, then zs_rocm_mpm_apply_boundary_transition on the new grid (single rank only).  max_vel is
@@ -708,7 +741,15 @@ class MpmTransfer:
             return
         if getattr(self, "grid2", None) is None or self.grid2.numel() != self.grid.numel():
             self.grid2 = torch.empty_like(self.grid)
-        src, dst = self.grid, self.grid2
+            self._grids_written()
+        rotate = self.side == 8 and self.rotate_grids
+        if rotate and (self.grid3 is None or self.grid3.numel() != self.grid.numel() or self.grid3 is self.grid or self.grid3 is self.grid2):
+            self.grid3 = torch.empty_like(self.grid)
+            self._grids_written()
+        src, dst, clr = self.grid, self.grid2, (self.grid3 if rotate else None)
+        clean = self._clean_grid
+        dst_is_clear = rotate and clean is not None and clean[0] is dst and clean[1] is self.table
+        self._clean_grid = None   # (until this call has succeeded)
         a = getattr(self, "_step_args", None)
         if a is None:
             a = self._step_args = MpmStep()
@@ -716,6 +757,8 @@ class MpmTransfer:
         a.particles = self.particles()
         a.table = self.table.handle
         a.gridA, a.gridB = src.data_ptr(), dst.data_ptr()
+        a.gridClear = clr.data_ptr() if clr is not None else None   # the block kernel clears it: the target of the NEXT step
+        a.gridBIsClear = int(dst_is_clear)                          # this step's target was cleared that way: no memset
         a.nblocks = self.nblocks
         a.storage = C.addressof(self.slot_storage)
         a.writeAll = int(write_all)
@@ -741,7 +784,11 @@ class MpmTransfer:
             # continuation is valid)
             self._poisoned = True
             raise RuntimeError("zs_rocm_mpm_step_slotted failed: the step is half applied (particles advanced, grids not): this object cannot be stepped again")
-        self.grid, self.grid2 = dst, src
+        if rotate:
+            self.grid, self.grid2, self.grid3 = dst, clr, src
+            self._clean_grid = (clr, self.table)
+        else:
+            self.grid, self.grid2 = dst, src
 
     def margin_violated(self):
         """True if, since construction, an exact-path particle was ever farther than one bin from its bin during a fused step
