@@ -961,6 +961,69 @@ ZS_ROCM_EXPORT int zs_rocm_mesh_elastic_gradient(zs_rocm_policy *, const zs_rocm
                                                  float *scratch, float *triEnergy, float *hingeEnergy, double *total, float *grad, int *status);
 ZS_ROCM_EXPORT int zs_rocm_mesh_elastic_hessian_product(zs_rocm_policy *, const zs_rocm_mesh *, const float *verts, float mu, float lam,
                                                         float kb, int psd, const float *x, float *scratch, float *hx, int *status);
+/* ---- mesh Newton system (zpc_amd/csrc/mesh_solve.hip, include/zensim_rocm/solve_device.hpp): the linear system of one Newton iteration of
+ * the incremental potential, A = diag(mass) + scale (H+_elastic + H+_barrier + H_friction) on [nv][3] float32 vectors (scale = h^2 for
+ * backward Euler), its per-vertex 3 x 3 diagonal blocks, the operator and a block-Jacobi preconditioned conjugate-gradient solve whose
+ * scalars stay on the device.  The terms are the products above with psd != 0 (friction as it stands); each is optional.
+ *   descriptor  mass [nv]; fixed [nv] bytes or NULL (non-zero: a Dirichlet vertex; a vertex whose mass is not finite and positive is
+ *               treated as fixed too); scale (finite; a negative one is accepted and makes the solve break down); elastic != 0: mu, lam,
+ *               kb as for the elastic product; barrier != 0: the two lists, their incidence (zs_rocm_mesh_barrier_incidence), dHat, kappa,
+ *               mollify; friction != 0: the displacement u [nv][3], the lag step's lists (they may differ from the barrier's), their
+ *               incidence, the records, fmu, epsv.  verts: the trial positions of the elastic and the barrier term, NULL: the mesh's own.
+ *   sizes       sizes[0] = floats of scratch for multiply and solve (the per-element terms: elastic, barrier, friction, one behind the
+ *               other), sizes[1] = floats of scratch for blocks (twice that: six floats per corner), sizes[2] = nv.  size_t sizes[3].
+ *   blocks      a block is 6 floats (xx, xy, xz, yy, yz, zz); entry (i, j), i <= j, of a term's block at v is component i at v of that
+ *               term's product with the unit direction e_{v,j}, value for value: element kernels write every element's own corner blocks
+ *               with the product's own device function, a gather sums them per vertex in the product's run order.  elastic, barrier,
+ *               friction [nv][6]: the per-term blocks (zeros for a term that is absent); combined [nv][6] = scale ((elastic + barrier) +
+ *               friction) plus the mass on the diagonal; inverse [nv][6]: its inverse in closed form, the scalar Jacobi where that fails
+ *               (solve_device.hpp), zero at a fixed vertex.  status int[8] = elastic overflows (triangles, hinges), barrier zero-distance
+ *               pairs (PT, EE), friction overflows (PT, EE), inverse fallbacks, masses treated as fixed.  All five arrays are required.
+ *   multiply    q = A x: the element kernels of the three products write their per-element terms to scratch as they do in the product
+ *               calls, then one gather per vertex sums the elastic triangle run, the elastic hinge run, the barrier run and the friction
+ *               run into one float32 accumulator, each run front to back; q_v = mass_v x_v + scale acc_v, zero at a fixed vertex.
+ *   solve       preconditioned CG from x (in: the start, out: the solution) for the right-hand side b, z = inverse r, res = sqrt(r . z),
+ *               stopping at res <= min(relTol res0, tol) or after maxIters iterations.  Dot products: every product of two floats exact in
+ *               float64, summed in float64 in a fixed order; alpha and beta are float64 quotients rounded to float32 once on the device.
+ *               record: 2 + maxIters + 1 words on the device = iters (int), flag (int), the residual history (float, entry k after k
+ *               iterations).  flag: 1 converged, 2 maxIters reached, 3 breakdown (p . A p not positive), 4 a scalar that is not finite.
+ *               Once the flag is set x, iters and the history no longer change.  The host enqueues checkEvery >= 1 iterations at a time
+ *               and reads the flag once per batch; the result does not depend on checkEvery.
+ * Two calls give the same bytes (no float atomics).  -1 and nothing written for a NULL policy, mesh, descriptor, mass (with vertices) or
+ * output, whatever the sibling product call of a term that is present rejects, a scale that is not finite, maxIters < 0, checkEvery < 1. */
+typedef struct zs_rocm_mesh_system {
+  const float *mass;
+  const unsigned char *fixed;
+  float scale;
+  const float *verts;
+  int elastic;
+  float mu, lam, kb;
+  int barrier;
+  const int *ptPairs;
+  size_t npt;
+  const int *eePairs;
+  size_t nee;
+  const int *starts, *entries;
+  float dHat, kappa;
+  int mollify;
+  int friction;
+  const float *u;
+  const int *fPtPairs;
+  size_t fNpt;
+  const int *fEePairs;
+  size_t fNee;
+  const int *fStarts, *fEntries;
+  const float *record;
+  float fmu, epsv;
+} zs_rocm_mesh_system;
+ZS_ROCM_EXPORT int zs_rocm_mesh_system_sizes(const zs_rocm_mesh *, const zs_rocm_mesh_system *, size_t *sizes);
+ZS_ROCM_EXPORT int zs_rocm_mesh_system_blocks(zs_rocm_policy *, const zs_rocm_mesh *, const zs_rocm_mesh_system *, float *scratch, float *elastic,
+                                              float *barrier, float *friction, float *combined, float *inverse, int *status);
+ZS_ROCM_EXPORT int zs_rocm_mesh_system_multiply(zs_rocm_policy *, const zs_rocm_mesh *, const zs_rocm_mesh_system *, float *scratch,
+                                                const float *x, float *q);
+ZS_ROCM_EXPORT int zs_rocm_mesh_system_solve(zs_rocm_policy *, const zs_rocm_mesh *, const zs_rocm_mesh_system *, float *scratch,
+                                             const float *inverse, const float *b, float *x, int maxIters, float tol, float relTol,
+                                             int checkEvery, void *record);
 /* ---- mesh CCD (zpc_amd/csrc/mesh_ccd.hip, include/zensim_rocm/ccd_device.hpp): a conservative bound on the step t in [0, tMax] for which
  * verts + t dir (verts NULL: the mesh's own positions; dir [nv][3]) keeps every pair of the two lists free of contact, by additive CCD on
  * the unsigned distance -- what a line search needs before it may evaluate the barrier.  The reference has yes / no tests only

@@ -126,6 +126,17 @@ class MeshView(C.Structure):
                 ("edgeNormals", C.c_void_p), ("bvh", LBvhView), ("numVerts", C.c_int), ("numTris", C.c_int)]
 
 
+class MeshSystemDesc(C.Structure):
+    """zs_rocm_mesh_system: the terms of the mesh Newton system (include/zs_rocm.h)"""
+    _fields_ = [("mass", C.c_void_p), ("fixed", C.c_void_p), ("scale", C.c_float), ("verts", C.c_void_p),
+                ("elastic", C.c_int), ("mu", C.c_float), ("lam", C.c_float), ("kb", C.c_float),
+                ("barrier", C.c_int), ("ptPairs", C.c_void_p), ("npt", C.c_size_t), ("eePairs", C.c_void_p), ("nee", C.c_size_t),
+                ("starts", C.c_void_p), ("entries", C.c_void_p), ("dHat", C.c_float), ("kappa", C.c_float), ("mollify", C.c_int),
+                ("friction", C.c_int), ("u", C.c_void_p), ("fPtPairs", C.c_void_p), ("fNpt", C.c_size_t), ("fEePairs", C.c_void_p),
+                ("fNee", C.c_size_t), ("fStarts", C.c_void_p), ("fEntries", C.c_void_p), ("record", C.c_void_p), ("fmu", C.c_float),
+                ("epsv", C.c_float)]
+
+
 def _declare(L):
     vp, sz, i32, f32 = C.c_void_p, C.c_size_t, C.c_int, C.c_float
     L.policy__device.restype = vp
@@ -490,6 +501,13 @@ def _declare_containers(L):
     L.zs_rocm_mesh_elastic_energy.argtypes = [vp, vp, vp, f32, f32, f32, vp, vp, vp, vp]
     L.zs_rocm_mesh_elastic_gradient.argtypes = [vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp]
     L.zs_rocm_mesh_elastic_hessian_product.argtypes = [vp, vp, vp, f32, f32, f32, i32, vp, vp, vp, vp]
+    PS = C.POINTER(MeshSystemDesc)
+    L.zs_rocm_mesh_system_sizes.argtypes = [vp, PS, C.POINTER(C.c_size_t)]
+    L.zs_rocm_mesh_system_blocks.argtypes = [vp, vp, PS, vp, vp, vp, vp, vp, vp, vp]
+    L.zs_rocm_mesh_system_multiply.argtypes = [vp, vp, PS, vp, vp, vp]
+    L.zs_rocm_mesh_system_solve.argtypes = [vp, vp, PS, vp, vp, vp, vp, i32, f32, f32, i32, vp]
+    for name in ("system_sizes", "system_blocks", "system_multiply", "system_solve"):
+        getattr(L, "zs_rocm_mesh_" + name).restype = i32
     for name in ("friction_lag", "friction_energy", "friction_gradient", "friction_hessian_product", "set_rest_shape", "rest_shape_sizes",
                  "rest_shape", "elastic_energy", "elastic_gradient", "elastic_hessian_product"):
         getattr(L, "zs_rocm_mesh_" + name).restype = i32

@@ -1,7 +1,8 @@
 // mesh.hpp -- the triangle-mesh object of the C ABI, shared by mesh.hip (colliders, mesh -> level set), mesh_proximity.hip (the
 // point-triangle and edge-edge pairs within a contact distance), mesh_barrier.hip (the contact potential on those pairs), mesh_ccd.hip
 // (the largest step along a direction that keeps those pairs apart), mesh_elastic.hip (the membrane and bending energy of the mesh itself)
-// and mesh_terms.hip (incidence, gather and total behind the barrier, friction and elastic terms).
+// mesh_terms.hip (incidence, gather and total behind the barrier, friction and elastic terms) and mesh_solve.hip (the Newton system on those
+// terms: diagonal blocks, fused operator, preconditioned CG).
 #pragma once
 #include "common.hpp"
 #include "../../include/zensim_rocm/mesh_device.hpp"
@@ -145,12 +146,40 @@ struct TermRun {
   const int *starts, *entries;
   const float *terms;
 };
+// the rows of one run of vertex v, front to back (the gathers of mesh_terms.hip and mesh_solve.hip)
+__device__ __forceinline__ void terms_add_run(const int *__restrict__ starts, const int *__restrict__ entries, const float *__restrict__ terms, int v,
+                                              float &s0, float &s1, float &s2) {
+  for (int i = starts[v]; i < starts[v + 1]; ++i) {
+    const float *g = terms + 3 * (size_t)entries[i];
+    s0 += g[0];
+    s1 += g[1];
+    s2 += g[2];
+  }
+}
 // out [nv][3]: lane = vertex sums the rows of its nruns (1 or 2) runs, one run after the other, each front to back
 void terms_gather(Launch &L, const TermRun *runs, int nruns, size_t nv, float *out);
 // the float64 total of the floats a [na] then b [nb], summed in a fixed order
 void terms_total(Launch &L, const float *a, size_t na, const float *b, size_t nb, double *total);
 // the caller's two status counts or a temporary, zeroed
 int *terms_status(Launch &L, int *status);
+
+// ---- mesh_elastic.hip: what mesh_solve.hip launches inside its own Launch
+// the N vertex indices of element i of elems [n][N]; false: one is outside the mesh and the element is idle
+template <int N>
+__device__ __forceinline__ bool elastic_indices(const int *__restrict__ elems, size_t i, int nv, int (&idx)[N]) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    idx[k] = elems[N * i + k];
+    ok = ok && (unsigned)idx[k] < (unsigned)nv;
+  }
+  return ok;
+}
+bool elastic_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, float mu, float lam, float kb);
+// the element kernels of one operation (ELASTIC_OP_*): triangles, then hinges, whose terms follow the triangles' in scratch; st: two zeroed
+// counts
+void elastic_launch_status(Launch &L, const zs_rocm_mesh *m, const float *verts, float mu, float lam, float kb, int op, const float *dir,
+                           float *triEnergy, float *hingeEnergy, float *scratch, int *st);
 
 // mesh_proximity.hip: after new vertex positions -- the packed nodes are stale, the edge tree (if built) is refitted; -1 on failure
 int mesh_proximity_refit(zs_rocm_policy *pol, zs_rocm_mesh &m);

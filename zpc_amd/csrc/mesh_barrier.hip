@@ -18,9 +18,7 @@
 // Built with -ffp-contract=off (zpc_amd/build.py), as every translation unit behind tri_closest / ee_closest.
 #include <cfloat>
 
-#include "mesh.hpp"
-#include "../../include/zensim_rocm/barrier_device.hpp"
-#include "../../include/zensim_rocm/friction_device.hpp"
+#include "mesh_pairs.hpp"
 
 namespace zsr {
 
@@ -40,55 +38,6 @@ __device__ __forceinline__ void barrier_store(float *contrib, size_t pair, const
   o[0] = make_float4(g[0][0], g[0][1], g[0][2], g[1][0]);
   o[1] = make_float4(g[1][1], g[1][2], g[2][0], g[2][1]);
   o[2] = make_float4(g[2][2], g[3][0], g[3][1], g[3][2]);
-}
-
-enum {
-  BARRIER_OP_ENERGY,
-  BARRIER_OP_GRADIENT,
-  BARRIER_OP_PRODUCT,
-  BARRIER_OP_PRODUCT_PSD,
-  BARRIER_OP_LAG,                // friction: the lagged record at verts
-  BARRIER_OP_FRICTION_ENERGY,    // friction at the displacement verts, from the record
-  BARRIER_OP_FRICTION_GRADIENT,
-  BARRIER_OP_FRICTION_PRODUCT
-};
-
-// the friction record of pair i: 32-byte records in a 256-byte aligned array, as two float4
-__device__ __forceinline__ void friction_store(float *record, size_t pair, const FrictionRecord &r) {
-  float4 *o = reinterpret_cast<float4 *>(record + 8 * pair);
-  o[0] = make_float4(r.n[0], r.n[1], r.n[2], r.lambda);
-  o[1] = make_float4(r.w[0], r.w[1], r.w[2], r.w[3]);
-}
-__device__ __forceinline__ FrictionRecord friction_load(const float *record, size_t pair) {
-  const float4 *in = reinterpret_cast<const float4 *>(record + 8 * pair);
-  const float4 a = in[0], b = in[1];
-  return FrictionRecord{{a.x, a.y, a.z}, a.w, {b.x, b.y, b.z, b.w}};
-}
-
-// one pair list of one kind and what the pair kernel reads and writes for it
-struct BarrierPairs {
-  const float *verts;  // [nv][3] positions; a friction evaluation: the displacement u
-  const int *prims;    // the kind's primitives: tris [np][3] (PT) or edges [np][2] (EE)
-  int nv, np;
-  const float *rest;  // EE: the squared rest lengths [np]; null: unmollified
-  const int *pairs;   // [n][2]: (vertex, triangle) or (edge, edge)
-  int n;
-  float dHat2, kappa;
-  const float *dir;         // [nv][3], a product only
-  float *energy, *contrib;  // [n] (energy, gradient) and the [n][4][3] records (all but energy)
-  int *status;              // [2] zero-distance (a friction evaluation: overflow) counts, PT then EE
-  float *record;            // friction: the [n][8] records, written by the lag step and read by the evaluations
-  float mu, epsv;           // a friction evaluation: the coefficient and the static-friction threshold
-};
-
-// the four corner vertices of pair i (pair_corners of mesh.hpp; false: the pair is inactive) and the mollifier threshold (0: none)
-template <bool EE>
-__device__ __forceinline__ bool barrier_corners(const BarrierPairs &a, int i, int (&idx)[4], float &eps) {
-  eps = 0.f;
-  if (!pair_corners<EE>(a.pairs, a.prims, a.nv, a.np, i, idx)) return false;
-  if constexpr (EE)
-    if (a.rest) eps = barrier_ee_eps(a.rest[a.pairs[2 * (size_t)i]], a.rest[a.pairs[2 * (size_t)i + 1]]);
-  return true;
 }
 
 template <bool EE, int OP>
@@ -163,8 +112,8 @@ struct BarrierCornerVertex {
 };
 
 // the checks the energy, the gradient and the product have in common
-static bool barrier_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const int *ptPairs, size_t npt, const int *eePairs, size_t nee,
-                            float dHat, float kappa, int mollify) {
+bool barrier_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const int *ptPairs, size_t npt, const int *eePairs, size_t nee, float dHat,
+                     float kappa, int mollify) {
   if (!pol || !m || !m->stats || !(dHat > 0.f && dHat <= FLT_MAX) || !(kappa > 0.f && kappa <= FLT_MAX) || (mollify && !m->hasRest)) return false;
   return barrier_counts_ok(npt, nee) && !(npt && !ptPairs) && !(nee && !eePairs);
 }
@@ -176,22 +125,19 @@ static void barrier_launch_op(Launch &L, const BarrierPairs &pt, const BarrierPa
   if (ee.n) hipLaunchKernelGGL((barrier_pair_kernel<true, OP>), dim3(ceil_div(ee.n, BAR_BLOCK)), block, 0, L.stream, ee);
 }
 
-// what the friction operations add to a launch: the [npt + nee][8] records (PT pairs first), mu and the threshold
-struct FrictionArgs {
-  float *record;
-  float mu, epsv;
-};
-
-// the pair kernels of one operation: the PT list, then the EE list, whose records follow the PT list's
-static void barrier_launch_pairs(Launch &L, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
-                                 size_t nee, float dHat, float kappa, int mollify, int op, const float *dir, float *ptEnergy, float *eeEnergy,
-                                 float *scratch, int *status, const FrictionArgs &fr) {
-  const BarrierPairs pt = {verts ? verts : m->verts, m->tris, (int)m->nv, (int)m->nt, nullptr, ptPairs, (int)npt, dHat * dHat, kappa, dir,
-                           ptEnergy, scratch, terms_status(L, status), fr.record, fr.mu, fr.epsv};
-  BarrierPairs ee = pt;
+// the argument blocks of the PT and the EE list: the EE list's scratch (stride floats per pair) and records follow the PT list's
+void barrier_pair_args(const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs, size_t nee, float dHat,
+                       float kappa, int mollify, const float *dir, float *ptEnergy, float *eeEnergy, float *scratch, size_t stride, int *status,
+                       const FrictionArgs &fr, BarrierPairs &pt, BarrierPairs &ee) {
+  pt = {verts ? verts : m->verts, m->tris, (int)m->nv, (int)m->nt, nullptr, ptPairs, (int)npt, dHat * dHat, kappa, dir,
+        ptEnergy, scratch, status, fr.record, fr.mu, fr.epsv};
+  ee = pt;
   ee.prims = m->edges, ee.np = (int)m->ne, ee.rest = mollify ? m->restLen2 : nullptr;
-  ee.pairs = eePairs, ee.n = (int)nee, ee.energy = eeEnergy, ee.contrib = scratch ? scratch + 12 * npt : nullptr;
+  ee.pairs = eePairs, ee.n = (int)nee, ee.energy = eeEnergy, ee.contrib = scratch ? scratch + stride * npt : nullptr;
   ee.record = fr.record ? fr.record + 8 * npt : nullptr;
+}
+
+void barrier_launch_args(Launch &L, int op, const BarrierPairs &pt, const BarrierPairs &ee) {
   switch (op) {
     case BARRIER_OP_ENERGY: return barrier_launch_op<BARRIER_OP_ENERGY>(L, pt, ee);
     case BARRIER_OP_GRADIENT: return barrier_launch_op<BARRIER_OP_GRADIENT>(L, pt, ee);
@@ -204,9 +150,19 @@ static void barrier_launch_pairs(Launch &L, const zs_rocm_mesh *m, const float *
   }
 }
 
+// the pair kernels of one operation: the PT list, then the EE list; the status words (the caller's or a temporary) are zeroed first
+void barrier_launch_pairs(Launch &L, const zs_rocm_mesh *m, const float *verts, const int *ptPairs, size_t npt, const int *eePairs,
+                          size_t nee, float dHat, float kappa, int mollify, int op, const float *dir, float *ptEnergy, float *eeEnergy,
+                          float *scratch, int *status, const FrictionArgs &fr) {
+  BarrierPairs pt, ee;
+  barrier_pair_args(m, verts, ptPairs, npt, eePairs, nee, dHat, kappa, mollify, dir, ptEnergy, eeEnergy, scratch, 12, terms_status(L, status), fr,
+                    pt, ee);
+  barrier_launch_args(L, op, pt, ee);
+}
+
 // the checks the friction evaluations have in common
-static bool friction_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs,
-                             size_t nee, const float *record, float mu, float epsv) {
+bool friction_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const float *u, const int *ptPairs, size_t npt, const int *eePairs,
+                      size_t nee, const float *record, float mu, float epsv) {
   if (!pol || !m || !m->stats || !(mu >= 0.f && mu <= FLT_MAX) || !(epsv > 0.f && epsv <= FLT_MAX) || (m->nv && !u)) return false;
   return barrier_counts_ok(npt, nee) && !(npt && !ptPairs) && !(nee && !eePairs) && !(npt + nee && !record);
 }

@@ -76,17 +76,6 @@ __global__ __launch_bounds__(EL_BLOCK) void elastic_corner_starts_kernel(const u
   starts[v] = (int)lo;
 }
 
-template <int N>
-__device__ __forceinline__ bool elastic_indices(const int *__restrict__ elems, size_t i, int nv, int (&idx)[N]) {
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    idx[k] = elems[N * i + k];
-    ok = ok && (unsigned)idx[k] < (unsigned)nv;
-  }
-  return ok;
-}
-
 // the rest record of element i (16-byte records in a 256-byte aligned array); degenerate ones are counted
 template <bool HINGE>
 __global__ __launch_bounds__(EL_BLOCK) void elastic_rest_kernel(const float *__restrict__ verts, const int *__restrict__ elems, int nv, int n,
@@ -188,15 +177,14 @@ static void elastic_launch_op(Launch &L, const ElasticElems &tri, bool membrane,
   if (hinge.n && bending) hipLaunchKernelGGL((elastic_elem_kernel<true, HINGE_OP>), dim3(ceil_div(hinge.n, EL_BLOCK)), block, 0, L.stream, hinge);
 }
 
-static bool elastic_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, float mu, float lam, float kb) {
+bool elastic_args_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, float mu, float lam, float kb) {
   return pol && m && m->stats && m->hasRestShape && mu >= 0.f && mu <= FLT_MAX && lam >= 0.f && lam <= FLT_MAX && kb >= 0.f && kb <= FLT_MAX;
 }
 
 // the element kernels of one operation: triangles, then hinges, whose terms follow the triangles'; a kind that is skipped (zero stiffness)
-// gets zero bytes
-static void elastic_launch(Launch &L, const zs_rocm_mesh *m, const float *verts, float mu, float lam, float kb, int op, const float *dir,
-                           float *triEnergy, float *hingeEnergy, float *scratch, int *status) {
-  int *st = terms_status(L, status);
+// gets zero bytes; st: two zeroed counts
+void elastic_launch_status(Launch &L, const zs_rocm_mesh *m, const float *verts, float mu, float lam, float kb, int op, const float *dir,
+                           float *triEnergy, float *hingeEnergy, float *scratch, int *st) {
   const bool membrane = mu > 0.f || lam > 0.f, bending = kb > 0.f;
   const ElasticElems tri = {verts ? verts : m->verts, m->tris, (int)m->nv, (int)m->nt, m->triRecord, mu, lam, kb, dir, triEnergy, scratch, st};
   ElasticElems hinge = tri;
@@ -216,6 +204,12 @@ static void elastic_launch(Launch &L, const zs_rocm_mesh *m, const float *verts,
     case ELASTIC_OP_PRODUCT: return elastic_launch_op<ELASTIC_OP_PRODUCT>(L, tri, membrane, hinge, bending);
     default: return elastic_launch_op<ELASTIC_OP_PRODUCT_PSD>(L, tri, membrane, hinge, bending);
   }
+}
+
+// ... with the status words (the caller's or a temporary) zeroed first
+static void elastic_launch(Launch &L, const zs_rocm_mesh *m, const float *verts, float mu, float lam, float kb, int op, const float *dir,
+                           float *triEnergy, float *hingeEnergy, float *scratch, int *status) {
+  elastic_launch_status(L, m, verts, mu, lam, kb, op, dir, triEnergy, hingeEnergy, scratch, terms_status(L, status));
 }
 
 // per vertex the terms of its triangle run (entries 3 t + corner), then of its hinge run (4 h + corner, behind the triangles' terms)

@@ -31,16 +31,6 @@ void incidence_end(Launch &L, const IncidenceKeys &k, size_t n, size_t nv, int *
 }
 
 // ---------------------------------------------------------------------------------------------------------------- gather
-// the rows of one run of vertex v, front to back
-__device__ __forceinline__ void terms_add_run(const int *__restrict__ starts, const int *__restrict__ entries, const float *__restrict__ terms, int v,
-                                              float &s0, float &s1, float &s2) {
-  for (int i = starts[v]; i < starts[v + 1]; ++i) {
-    const float *g = terms + 3 * (size_t)entries[i];
-    s0 += g[0];
-    s1 += g[1];
-    s2 += g[2];
-  }
-}
 // (plain pointer arguments, not the TermRun structs: the compiler then loads every kernel argument ahead of the first run)
 template <int NRUNS>
 __global__ __launch_bounds__(TERM_BLOCK) void terms_gather_kernel(const int *__restrict__ starts0, const int *__restrict__ entries0,

@@ -3,7 +3,7 @@ edge pseudonormals) and answers closest-point and signed-distance queries and th
 contact distance), the IPC barrier potential with its gradient and Hessian-vector product on those pairs, the largest step along a
 direction that keeps them apart (max_step, step_candidates) and the mesh's own membrane and bending energy against a rest shape
 (set_rest_shape, elastic, elastic_hessian_product); SparseLevelSet.from_mesh (zpc_amd/levelset.py) turns one
-into a sparse level set.  Set-up code: torch for the plumbing; every query runs in the library's HIP kernels."""
+into a sparse level set, MeshSystem (zpc_amd/mesh_solve.py) puts the three Hessian products behind one linear system and solves it.  Set-up code: torch for the plumbing; every query runs in the library's HIP kernels."""
 import ctypes as C
 
 import numpy as np
