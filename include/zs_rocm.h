@@ -1024,6 +1024,41 @@ ZS_ROCM_EXPORT int zs_rocm_mesh_system_multiply(zs_rocm_policy *, const zs_rocm_
 ZS_ROCM_EXPORT int zs_rocm_mesh_system_solve(zs_rocm_policy *, const zs_rocm_mesh *, const zs_rocm_mesh_system *, float *scratch,
                                              const float *inverse, const float *b, float *x, int maxIters, float tol, float relTol,
                                              int checkEvery, void *record);
+/* ---- mesh incremental potential (zpc_amd/csrc/mesh_potential.hip, include/zensim_rocm/potential_device.hpp): the objective the Newton system
+ * above linearises, E(x) = 1/2 (x - target)^T M (x - target) + scale (Psi_elastic(x) + B(x) + D(x - start)), as one fused evaluation of energy
+ * and gradient and as a backtracking line search whose decisions stay on the device.  The terms come in a zs_rocm_mesh_system descriptor
+ * (mass, fixed, scale and the three optional terms as above; its verts and u are not read: the entries take the positions verts [nv][3],
+ * the inertia target [nv][3] and, required with friction, the positions start [nv][3] at the start of the step, u = verts - start).  The
+ * barrier's lists may be any proximity lists of the mesh with a radius of at least dHat: a pair at dHat or beyond adds exactly nothing.
+ *   sizes        sizes[0] = floats of scratch (the per-element gradient terms, laid out as for the system's multiply), sizes[1] = floats of
+ *                energies (one per vertex, then one per triangle, hinge, barrier pair, friction pair of the terms present), sizes[2] = nv.
+ *   evaluate     parts double[5] on the device = the inertia, elastic, barrier and friction energies, each the float64 fixed-order total of
+ *                its float32 per-element energies in the order of the public energy calls (whose totals they equal bit for bit), then
+ *                E = parts[0] + (double) scale ((parts[1] + parts[2]) + parts[3]).  grad [nv][3] or NULL (energy only: no scratch needed):
+ *                g = mass (x - target) + scale acc, acc one float32 accumulator over the elastic triangle run, the elastic hinge run, the
+ *                barrier run and the friction run of the vertex, each front to back; a fixed vertex has no inertia energy and a zero row.
+ *                status int[6] or NULL = elastic overflows (triangles, hinges), barrier zero-distance pairs (PT, EE), friction overflows.
+ *   line_search  backtracking from verts along dir [nv][3]: t_0 = tMax (tMaxDev != NULL: one device float, read in its place), t_{k+1} =
+ *                shrink t_k, x_k = verts + t_k dir (verts at a fixed vertex); trial k is accepted iff E_k is finite and
+ *                E_k <= E_0 + ((double) c1 (double) t_k) slope, slope = grad . dir in float64.  record on the device: int trials, int flag,
+ *                float t (the accepted step, else 0), float (the next trial's step), double energy (of the accepted trial, else E_0),
+ *                double slope, double history[maxTrials + 1] (E_0, then one entry per trial): 32 + 8 (maxTrials + 1) bytes.  flag: 1
+ *                accepted, 2 maxTrials reached, 3 slope not negative, 4 E_0, slope or tMax not finite or tMax <= 0.  x [nv][3]: the accepted
+ *                trial, else a copy of verts; it must not alias verts or dir.  Once the flag is set nothing of the record changes.  The host
+ *                enqueues checkEvery >= 1 trials at a time and reads the flag once per batch; the result does not depend on checkEvery.
+ *                No collision check is made: a trial across a pair has a finite barrier energy again, so tMax has to come from
+ *                zs_rocm_mesh_ccd.
+ * Two calls give the same bytes (no float atomics).  -1 and nothing written for a NULL policy, mesh, descriptor, mass, target, verts (with
+ * vertices) or output, friction without start, whatever the system entries reject, c1 negative or not finite, shrink outside (0, 1),
+ * maxTrials < 1, checkEvery < 1. */
+ZS_ROCM_EXPORT int zs_rocm_mesh_potential_sizes(const zs_rocm_mesh *, const zs_rocm_mesh_system *, size_t *sizes);
+ZS_ROCM_EXPORT int zs_rocm_mesh_potential_evaluate(zs_rocm_policy *, const zs_rocm_mesh *, const zs_rocm_mesh_system *, const float *target,
+                                                   const float *start, const float *verts, float *scratch, float *energies, double *parts,
+                                                   float *grad, int *status);
+ZS_ROCM_EXPORT int zs_rocm_mesh_potential_line_search(zs_rocm_policy *, const zs_rocm_mesh *, const zs_rocm_mesh_system *, const float *target,
+                                                      const float *start, const float *verts, const float *dir, float tMax,
+                                                      const float *tMaxDev, float c1, float shrink, int maxTrials, int checkEvery,
+                                                      float *scratch, float *energies, float *x, void *record);
 /* ---- mesh CCD (zpc_amd/csrc/mesh_ccd.hip, include/zensim_rocm/ccd_device.hpp): a conservative bound on the step t in [0, tMax] for which
  * verts + t dir (verts NULL: the mesh's own positions; dir [nv][3]) keeps every pair of the two lists free of contact, by additive CCD on
  * the unsigned distance -- what a line search needs before it may evaluate the barrier.  The reference has yes / no tests only

@@ -506,6 +506,9 @@ def _declare_containers(L):
     L.zs_rocm_mesh_system_blocks.argtypes = [vp, vp, PS, vp, vp, vp, vp, vp, vp, vp]
     L.zs_rocm_mesh_system_multiply.argtypes = [vp, vp, PS, vp, vp, vp]
     L.zs_rocm_mesh_system_solve.argtypes = [vp, vp, PS, vp, vp, vp, vp, i32, f32, f32, i32, vp]
+    L.zs_rocm_mesh_potential_sizes.argtypes = [vp, PS, C.POINTER(C.c_size_t)]
+    L.zs_rocm_mesh_potential_evaluate.argtypes = [vp, vp, PS, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.zs_rocm_mesh_potential_line_search.argtypes = [vp, vp, PS, vp, vp, vp, vp, f32, vp, f32, f32, i32, i32, vp, vp, vp, vp]
     for name in ("system_sizes", "system_blocks", "system_multiply", "system_solve"):
         getattr(L, "zs_rocm_mesh_" + name).restype = i32
     for name in ("friction_lag", "friction_energy", "friction_gradient", "friction_hessian_product", "set_rest_shape", "rest_shape_sizes",

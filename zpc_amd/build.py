@@ -45,7 +45,10 @@ EXTRA_FLAGS = {"mpm_slotted.hip": ["-fno-slp-vectorize"], "mpm_slotblk.hip": ["-
                # the gather and the total behind those terms: float32 and float64 sums that the tests replay addition by addition
                "mesh_terms.hip": ["-ffp-contract=off"],
                # the Newton system on those terms (include/zensim_rocm/solve_device.hpp): blocks, operator and solve are replayed bit for bit
-               "mesh_solve.hip": ["-ffp-contract=off"]}
+               "mesh_solve.hip": ["-ffp-contract=off"],
+               # the incremental potential on those terms (include/zensim_rocm/potential_device.hpp): energy, gradient and the line search's
+               # decisions are replayed bit for bit
+               "mesh_potential.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst):

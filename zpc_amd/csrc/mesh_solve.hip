@@ -32,7 +32,7 @@
 // Built with -ffp-contract=off (zpc_amd/build.py): tests/ref64_solve.py replays blocks, operator and solve operation by operation.
 #include <cfloat>
 
-#include "mesh_pairs.hpp"
+#include "mesh_system.hpp"
 #include "../../include/zensim_rocm/elastic_device.hpp"
 #include "../../include/zensim_rocm/solve_device.hpp"
 
@@ -360,34 +360,7 @@ __global__ __launch_bounds__(SOLVE_BLOCK) void solve_direction_kernel(const floa
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-// where the terms of the three products sit in the scratch array (floats per corner: 3 for the operator, 6 for the blocks)
-struct SystemLayout {
-  size_t elastic, barrier, friction, total;
-};
-static SystemLayout system_layout(const zs_rocm_mesh *m, const zs_rocm_mesh_system &s, size_t perCorner) {
-  SystemLayout l;
-  const auto pad = [](size_t n) { return (n + 63) & ~(size_t)63; };  // every part starts 256-byte aligned (the pair kernels store float4)
-  l.elastic = 0;
-  l.barrier = s.elastic ? pad(perCorner * (3 * m->nt + 4 * m->nh)) : 0;
-  l.friction = l.barrier + (s.barrier ? pad(perCorner * 4 * (s.npt + s.nee)) : 0);
-  l.total = l.friction + (s.friction ? pad(perCorner * 4 * (s.fNpt + s.fNee)) : 0);
-  return l;
-}
-
-// the checks every entry has in common: each term that is present passes the checks of its own product call
-static bool system_ok(const zs_rocm_policy *pol, const zs_rocm_mesh *m, const zs_rocm_mesh_system *s) {
-  if (!pol || !m || !m->stats || !s || (m->nv && !s->mass) || !(fabsf(s->scale) <= FLT_MAX)) return false;
-  if (s->elastic && !elastic_args_ok(pol, m, s->mu, s->lam, s->kb)) return false;
-  if (s->barrier) {
-    if (!barrier_args_ok(pol, m, s->ptPairs, s->npt, s->eePairs, s->nee, s->dHat, s->kappa, s->mollify)) return false;
-    if (m->nv && (!s->starts || (s->npt + s->nee && !s->entries))) return false;
-  }
-  if (s->friction) {
-    if (!friction_args_ok(pol, m, s->u, s->fPtPairs, s->fNpt, s->fEePairs, s->fNee, s->record, s->fmu, s->epsv)) return false;
-    if (m->nv && (!s->fStarts || (s->fNpt + s->fNee && !s->fEntries))) return false;
-  }
-  return true;
-}
+// (SystemLayout, system_layout and system_ok: mesh_system.hpp, shared with mesh_potential.hip)
 
 // the element kernels of the three products for the direction dir into scratch; st: six zeroed counts (elastic, barrier, friction)
 static void system_launch_terms(Launch &L, const zs_rocm_mesh *m, const zs_rocm_mesh_system &s, const SystemLayout &l, const float *dir,
