@@ -173,6 +173,19 @@ struct StencilNodeLane {
     const float *c = st + (4 + 4 * ((S::STRESS ? 3 : 0) + S::D0 + q - (S::MASS ? 1 : 0))) * 64;
     return Wt * fmaf(c[192], oc[2], fmaf(c[128], oc[1], fmaf(c[64], oc[0], c[0])));
   }
+  // what the record adds to this node in ALL seven grid channels (v[0] mass, v[1 + j] staged channel j: the sets' accumulators in grid
+  // order, each the expression of value<CS>); every staged value is read before the first is used
+  __device__ __forceinline__ void values(const float *st, float Wt, float (&v)[7]) const {
+    float c[6][4];
+    const float m = st[0];
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) c[j][k] = st[(4 + 4 * j + k) * 64];
+    v[0] = Wt * m;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[1 + j] = Wt * fmaf(c[j][3], oc[2], fmaf(c[j][2], oc[1], fmaf(c[j][1], oc[0], c[j][0])));
+  }
 };
 
 // fused G2P2G launch for one block side: defined in mpm_fused_impl.hpp, instantiated in mpm_fused4.hip / mpm_fused8.hip (the

@@ -26,7 +26,11 @@
 //     loads and stores share vmcnt, so a spill reload inside the chunk loop waits for the record prefetch of the next chunk and for the
 //     particle stores just issued (profiles/r05_block_kernel.md, section 7; tests/test_host_cpu.py keeps it that way);
 //   * the bin's P2G arena has 8^3 nodes (ArenaBin8): a mover into a neighbour bin adds its 27 node terms there (plain LDS
-//     read-add-write) and they reach the grid with the bin's one flush -- no global atomics per mover;
+//     read-add-write) and they reach the grid with the bin's one flush -- no global atomics per mover.  ONE consumer wave (LIST_CS, the
+//     set with one accumulator per node) scatters a chunk's list for all seven channels: decode, weights, arena offset and face bits
+//     once per entry instead of once per set (91 VALU per pass of two entries against 247 over the four waves).  The other consumers
+//     wait at a bin's end, on an LDS word, until that wave has finished the bin's last list; the barrier that hands the next bin's
+//     first chunk over keeps its list behind their flush (blk_consumer; profiles/block_list.md);
 //   * the flush visits what can be non-zero, not the 512 nodes: the 6^3 core the register planes write (4 dense passes) and those 8 x 8
 //     faces of the shell a list entry of the bin has reached (a 6-bit mask kept while the lists are scattered; none at rest).  Every LDS
 //     read of a pass is issued before the first is used, and a pass writes zero over what it read: the arena is cleared once per
@@ -47,6 +51,7 @@ namespace zsr {
 
 constexpr int SB_NG = 5;       // ring: the four groups of a chunk + the group a straddling round keeps alive
 constexpr int SB_MAXCH = 64;   // chunks per block: 8 bins x (32 rounds x 64 cells / 256)
+constexpr int LIST_CS = 3;     // the consumer wave that scatters the chunks' lists: one accumulator per node, the most free registers
 
 struct SubGeom {  // what the shared scatter helpers need of a bin: origin inside the block, origin in world cells
   int o[3], org[3];
@@ -77,6 +82,8 @@ struct BlkShared {
   int *oc;                                   // [8] per bin: outbox records (after the bin has been finished)
   const unsigned *desc;                      // [SB_MAXCH + 5] desc[g + 1] = packed descriptor of chunk g (ChunkDesc), zero outside [0, G)
   unsigned *done;                            // consumer waves x chunks consumed
+  unsigned *listDone;                        // chunks whose list the list wave has scattered into the bin's arena
+  unsigned *faces;                           // [2] by bin parity: faces of the arena's shell the bin's lists have reached (blk_xlist_lds)
   int *sums;                                 // [0] sent, [1] homed, [2] bins whose outbox holds records that still have to be scattered
 };
 
@@ -150,15 +157,16 @@ struct ArenaBin8 {
   __device__ static constexpr int at(int x, int y, int z) { return x * SX + y * SY + z; }
 };
 
-// The chunk's list (movers into neighbour bins, arrival-queue overflow, stayers whose local position rounded onto 1.5): the channels of
-// set CS of their 27 node terms into the bin's 8^3 arena `pa` (this wave's channels).  Two list entries per pass, lane = (entry parity,
-// stencil node); the two entries of a pass may share nodes, so the halves do their read-add-write one after the other (LDS operations of
-// a wave execute in order).  Weights and values: StencilNodeLane, as slot_xlist_scatter.
+// The chunk's list (movers into neighbour bins, arrival-queue overflow, stayers whose local position rounded onto 1.5): ALL SEVEN grid
+// channels of their 27 node terms into the bin's 8^3 arena `parena`, by ONE wave (the consumer of set 3, blk_consumer).  Two list entries
+// per pass, lane = (entry parity, stencil node): the entry's decode, its three axis weights, the node's arena offset and the face bits
+// are formed once and serve seven values and seven read-add-writes (the seven reads of a half issued together).  The two entries of a
+// pass may share nodes, so the halves do their read-add-write one after the other (LDS operations of a wave execute in order).
+// Weights and values: StencilNodeLane, as slot_xlist_scatter -- term by term what the four per-set passes of this list added before
+// (profiles/block_list.md), in the same order.
 // `faces` (per lane, ORed): the faces of the arena's shell the entries of this lane reach -- bit 2 d: node 0 of the stencil sits on arena
 // coordinate 0 of axis d (the entry's coordinate is 0), bit 2 d + 1: node 2 sits on coordinate 7 (the entry's coordinate is 5).
-template <int CS>
-__device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned *xq, int nx, int lane, float *pa, unsigned &faces) {
-  using S = ConsumerSet<CS>;
+__device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned *xq, int nx, int lane, float *parena, unsigned &faces) {
   using A8 = ArenaBin8;
   const int node = lane & 31, half = lane >> 5;
   if (nx <= 0) return;
@@ -167,7 +175,7 @@ __device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned
   for (int k0 = 0; k0 < nx; k0 += 2) {
     const int k = k0 + half;
     const bool act = node < 27 && k < nx;
-    float val[S::NA];
+    float val[7];
     int an = 0;
     if (act) {
       const unsigned e = xq[k];
@@ -179,14 +187,16 @@ __device__ __forceinline__ void blk_xlist_lds(const float *stage, const unsigned
       const int ex = (int)((e >> 10) & 7u), ey = (int)((e >> 13) & 7u), ez = (int)((e >> 16) & 7u);
       an = A8::at(ex + sn.sel[0], ey + sn.sel[1], ez + sn.sel[2]);
       faces |= (ex == 0 ? 1u : 0u) | (ex == 5 ? 2u : 0u) | (ey == 0 ? 4u : 0u) | (ey == 5 ? 8u : 0u) | (ez == 0 ? 16u : 0u) | (ez == 5 ? 32u : 0u);
-#pragma unroll
-      for (int q = 0; q < S::NA; ++q) val[q] = sn.value<CS>(st, Wt, q);
+      sn.values(st, Wt, val);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if (act && half == h) {
+        float a[7];
 #pragma unroll
-        for (int q = 0; q < S::NA; ++q) pa[q * A8::CH + an] += val[q];
+        for (int q = 0; q < 7; ++q) a[q] = parena[q * A8::CH + an];
+#pragma unroll
+        for (int q = 0; q < 7; ++q) parena[q * A8::CH + an] = a[q] + val[q];
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
@@ -318,7 +328,7 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
 #pragma unroll
     for (int q = 0; q < S::NA; ++q) acc[k][q] = 0.f;
   unsigned mask = 0u;
-  unsigned faces = 0u;  // faces of the arena's shell the lists of the current bin have reached (blk_xlist_lds)
+  unsigned faces = 0u;  // (list wave) faces of the arena's shell the lists of the current bin have reached (blk_xlist_lds)
   int r = 0, off = 0;  // next round to consume, entry number of its first particle
   // The bin's arena (this wave's channels) is cleared HERE, once: every flush leaves it all zero again (see the bin end below), and the
   // padding of the 68-float stride is never written.
@@ -388,19 +398,35 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
       }
       if (spos >= 0) g2p2g_consume_set<CS>(mp, stage, spos, acc);
     }
-    {
+    if (CS == 0 && lane == 0) sh.xCnt[(g + 2) % 3] = 0u;  // (last read by the list wave with chunk g - 1)
+    if (CS == LIST_CS) {
+      // The chunk's list, all seven channels, by this wave alone.  It writes into channels the other three consumers flush, so:
+      //   * bin end: a set wave adds its planes and flushes only after listDone has reached this chunk (below) -- an LDS word this wave
+      //     alone writes, behind a release fence, like s_done; no barrier inside the chunk loop;
+      //   * next bin: this wave's first write for the next bin comes behind the barrier "chunk g + 1 staged" at the top of the next
+      //     iteration, which every set wave reaches only after it has flushed and zeroed this bin.  That barrier must stay in front of the list.
       const int nx = sh.xCnt[par] < (unsigned)SL_XQ ? (int)sh.xCnt[par] : SL_XQ;
-      if (CS == 0 && lane == 0) sh.xCnt[(g + 2) % 3] = 0u;
-      blk_xlist_lds<CS>(stage, sh.xq[par], nx, lane, pa, faces);
+      blk_xlist_lds(stage, sh.xq[par], nx, lane, sh.parena, faces);
+      if (d[1].last()) {  // the faces of the shell the bin's lists have reached, for all four flushing waves (one word per bin parity)
+        unsigned fm = 0u;
+#pragma unroll
+        for (int f = 0; f < 6; ++f) fm |= __ballot((faces >> f) & 1u) != 0ull ? 1u << f : 0u;
+        faces = 0u;
+        if (lane == 0) sh.faces[d[1].qp()] = fm;
+      }
     }
     // this wave has read what it needs of chunk g: the producers may stage chunk g + 1 over it
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) atomicAdd(sh.done, 1u);
+    if (lane == 0) {
+      if (CS == LIST_CS) __hip_atomic_store(sh.listDone, (unsigned)(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      atomicAdd(sh.done, 1u);
+    }
     binState(g, d[3], d[4]);
     if (CS == 3 && d[1].last()) blk_finish_bin(sh, A, blk * 8, b, d[1].qp(), lane);
     if (d[1].last()) {
-      // last chunk of the bin: the set's channels of the bin's arena belong to this wave alone -- add the 27 register planes on top of
-      // the lists' terms (phases ordered inside the wave), send the arena's nodes to the grid; no other wave is involved.
+      // last chunk of the bin: once the list wave is through with it, the set's channels of the bin's arena belong to this wave alone
+      // until the next bin's first barrier -- add the 27 register planes on top of the lists' terms (phases ordered inside the wave),
+      // send the arena's nodes to the grid.
       //   * The register planes write the 6^3 CORE of the arena only (coordinates 1..6): it is flushed densely, 216 nodes in 4 passes
       //     (the 40 idle lanes of the last pass read and zero a padding word).  A bin sits at offset 0 or 4 of its block, so a core node
       //     lies in this block or in its +1 neighbour per axis.
@@ -412,6 +438,10 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
       //   * Every pass writes zero over what it has read (LDS operations of a wave execute in order), so after the flush the wave's
       //     channels are all zero again -- core: every node visited; shell: zero unless flagged -- and the next bin's lists add into a
       //     clear arena without a clear loop of their own.
+      if (CS != LIST_CS) {  // the list wave has finished the list of this chunk, the bin's last: its terms are in this wave's channels
+        while (__hip_atomic_load(sh.listDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < (unsigned)(g + 1)) __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      }
       acc_to_arena<AL, true>(pa + AL::at(cx + 1, cy + 1, cz + 1), acc);  // (and the planes are zero again for the next bin)
       const SubGeom sg = sub_geom(borg, b);
       // (the lane number made opaque: the node offsets below depend on the lane alone, and hoisted out of the chunk loop they would be
@@ -432,10 +462,7 @@ __device__ __forceinline__ void blk_consumer(const MpmDev &mp, const int (&borg)
         }
         blk_flush_nodes<CS, 4, true>(pa, aoff, gx, gy, gz, sh.nbrBlk, A);
       }
-      unsigned fm = 0u;  // (wave-uniform)
-#pragma unroll
-      for (int f = 0; f < 6; ++f) fm |= __ballot((faces >> f) & 1u) != 0ull ? 1u << f : 0u;
-      faces = 0u;
+      unsigned fm = (unsigned)__builtin_amdgcn_readfirstlane((int)sh.faces[d[1].qp()]);  // (written by the list wave in front of listDone)
 #pragma unroll 1
       while (fm) {
         const int f = __builtin_ctz(fm);
@@ -483,11 +510,11 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   __shared__ int s_total[8], s_gbase[8], s_binQ[8], s_oc[8];
   __shared__ unsigned char s_chBin[SB_MAXCH], s_chIdx[SB_MAXCH];
   __shared__ unsigned s_desc[SB_MAXCH + 5];
-  __shared__ unsigned s_done;
+  __shared__ unsigned s_done, s_listDone, s_faces[2];
   __shared__ int s_sums[3], s_G;
   __shared__ float *s_clear;  // this block of A.gridClear (NULL: none), parked here from the head to the tail of the kernel
   const BlkShared sh{s_varena, s_parena, s_stage, s_smask, s_tab, s_masks, s_clr, s_arrLocal, s_arrCnt, s_arrQ, s_xCnt, s_xq, s_nbrBlk, s_nbrBin, s_nbr8,
-                     s_cnt, s_oc, s_desc, &s_done, s_sums};
+                     s_cnt, s_oc, s_desc, &s_done, &s_listDone, s_faces, s_sums};
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int blk = (int)blockIdx.x + A.binBase / 8;
   const int bin0 = blk * 8;
@@ -510,6 +537,7 @@ static __global__ __launch_bounds__(512, 4) void g2p2g_slotblk_kernel(MpmDev mp,
   if (tid < 8) (&s_cnt[0][0])[tid] = 0;
   if (tid == 0) {
     s_done = 0u;
+    s_listDone = 0u;
     s_clear = A.gridClear ? A.gridClear + (size_t)blk * 7 * NC : nullptr;
   }
   if (tid >= 64 && tid < 64 + 27) s_nbrBlk[tid - 64] = A.nbr27[(size_t)blk * 27 + (tid - 64)];
